@@ -41,7 +41,19 @@ factor 16, 1.07B edges at 26): strong scaling, dst rows partitioned as above,
 heavy rows chunked. Its CPU baseline is the reference product on a sample of
 that graph (rank 0, after the timed region).
 
-Run: python bench.py [--gpus N --steps K --warmup W]
+A plain run does what the headline needs and no more: setup, W warm-up steps,
+the K timed steps, the line (its roofline block from the timed region's own
+events; cpu_baseline null). Everything else above and below (the rocprofv3
+PMC passes behind roofline.traffic, cpu_baseline, the one_launch, train_step,
+model, rmat and sage_rmat legs, at N > 1 the halo_exchange, halo_bf16 and
+strong blocks) runs with --full, where the --no-* options drop single legs.
+
+--dump-outputs DIR: after the timed steps rank 0 writes what the last timed
+step returned to its caller as DIR/h_out.npy (fp32; the rows of a seeded
+sample when the whole output would pass DUMP_BYTES). Graph and features are
+seeded, so two runs with the same arguments see identical inputs.
+
+Run: python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
 """
 from __future__ import absolute_import
 
@@ -97,6 +109,13 @@ def build_parser():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run the PMC passes, the CPU baselines and "
+                         "every secondary leg (the --no-* options below drop single ones); "
+                         "without it only the headline is set up, timed and printed")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the output of the last timed step to DIR/h_out.npy (fp32; a "
+                         "seeded sample of its rows when it is larger than DUMP_BYTES)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-sample-edges", type=int, default=10_000_000)
     ap.add_argument("--no-traffic", action="store_true",
@@ -155,6 +174,15 @@ def build_parser():
                     help="cpu: run every leg through the library's host kernels with gloo "
                          "(tests of the launcher and the multi-rank plumbing; not a driver line)")
     return ap
+
+
+def headline_only(args):
+    """Without --full every pass and leg beside the headline is off."""
+    if not args.full:
+        args.no_traffic = args.no_cpu_baseline = args.no_bf16_leg = args.no_train_leg = True
+        args.no_rmat_leg = args.no_model_legs = args.no_strong_leg = True
+        args.no_one_launch_leg = args.no_sage_rmat_leg = True
+    return args
 
 
 # ---------------------------------------------------------------------------
@@ -299,6 +327,36 @@ def world_mismatch(args, env):
 def _sync(dev):
     if dev.type == "cuda":
         torch.cuda.synchronize(dev)
+
+
+# --dump-outputs writes at most this much (the headline's whole output is
+# 119 MB; files of up to 64 MB are compared build against build)
+DUMP_BYTES = 48 * 10 ** 6
+
+
+def dump_outputs(path, arrays):
+    """Write each tensor of ``arrays`` (name -> the rows a caller of the timed
+    step received) as ``path/<name>.npy`` in fp32 (fp64 stays fp64). Together
+    they take at most DUMP_BYTES: of a larger tensor a sample of its rows is
+    written, in row order, drawn by a generator seeded with 0 (the same rows
+    for the same shape, whatever the build or the device)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BYTES // max(len(arrays), 1)
+    for name, t in sorted(arrays.items()):
+        t = t.detach()
+        if t.dtype != torch.float64:
+            t = t.float()
+        t = t.reshape(t.shape[0], -1) if t.dim() > 1 else t.reshape(-1, 1)
+        keep = share // (t.shape[1] * t.element_size())
+        if t.shape[0] > keep:
+            pick = torch.Generator()
+            pick.manual_seed(0)
+            rows = torch.randperm(t.shape[0], generator=pick)[:keep].sort().values
+            t = t[rows.to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy())
+        log("dumped %s: %d x %d %s to %s" % (name, t.shape[0], t.shape[1],
+                                              str(t.dtype).replace("torch.", ""), path))
 
 
 def algorithmic_bytes(num_edges, num_rows, feat):
@@ -462,11 +520,12 @@ def _window_marker(dev):
         torch.cuda._sleep(1)
 
 
-def timed_steps(step, steps, warmup, world, dev):
+def timed_steps(step, steps, warmup, world, dev, last=None):
     """W warm-up steps, then K steps bracketed by barrier + synchronize; returns
     (max-over-ranks seconds, this rank's g-SpMM kernel ms per step). On the
     host path (no device launches to time) the kernel ms is the rank's own
-    wall time per step.
+    wall time per step. ``last``: a list that receives what the last timed
+    step returned (--dump-outputs).
 
     Kernel ms: the GPU span of every g-SpMM call of the step between two
     events on the stream the library launches on (kernel.timing_enable
@@ -491,10 +550,14 @@ def timed_steps(step, steps, warmup, world, dev):
         _window_marker(dev)  # tools/window_stats.py: the timed region's kernels
         _sync(dev)
         t_start = time.perf_counter()
-        for _ in range(steps):
+        for _ in range(steps - 1):
             step()
+        out = step()
         _sync(dev)
         own = time.perf_counter() - t_start
+        if last is not None:
+            last.append(out)
+        del out
         if dist.is_initialized():
             dist.barrier()
         elapsed = time.perf_counter() - t_start
@@ -926,7 +989,10 @@ def _claim_stdout():
 
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else list(argv)
-    args = build_parser().parse_args(argv)
+    ap = build_parser()
+    args = headline_only(ap.parse_args(argv))
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     cmd = launch_command(args, argv, os.environ)
     if cmd is not None:
         # N ranks, one process per GPU: the child torchrun starts them; this
@@ -1030,7 +1096,7 @@ def main(argv=None):
         num_local_edges, num_rows = num_edges_total, n
 
         def step():
-            kernel.gspmm(adj, "copy_u", "sum", h)
+            return kernel.gspmm(adj, "copy_u", "sum", h)
         parallelism = "single GPU (kernel API; heavy rows chunked)"
     elif not dist.is_initialized() and args.emulate_world > 1:
         from dgl.distributed import balanced_bounds
@@ -1058,7 +1124,7 @@ def main(argv=None):
                 buf.uniform_(-1, 1)
 
             def step():
-                pg.update_all(h_local)
+                return pg.update_all(h_local)
             blocks = pipelined_blocks(pg)
             mode = ("pipelined segments (own + all-to-allv halo of %d rows in %d chunks)"
                     % (pg.num_halo, args.pipeline_chunks)
@@ -1069,7 +1135,7 @@ def main(argv=None):
             h = torch.rand(n, FEAT, generator=gen, device=dev) * 2 - 1
 
             def step():
-                kernel.gspmm(adj, "copy_u", "sum", h)
+                return kernel.gspmm(adj, "copy_u", "sum", h)
             blocks = kernel.blocked_schedule(adj, h)
             mode = "one g-SpMM"
         del sel
@@ -1120,7 +1186,7 @@ def main(argv=None):
         num_local_edges, num_rows = pg.num_edges, pg.num_local
 
         def step():
-            pg.update_all(h_local)
+            return pg.update_all(h_local)
         parallelism = describe_partition(pg, world, args)
         blocks = pipelined_blocks(pg)
         nsw = sweep_segments(pg) if pg.halo_dtype is None else 0
@@ -1134,7 +1200,13 @@ def main(argv=None):
         log("setup done in %.1fs; peak HBM %.1f GB" % (
             time.time() - t0, torch.cuda.max_memory_allocated(dev) / 1e9))
 
-    elapsed, kernel_ms = timed_steps(step, args.steps, args.warmup, world, dev)
+    last = [] if args.dump_outputs and rank == 0 else None
+    elapsed, kernel_ms = timed_steps(step, args.steps, args.warmup, world, dev, last)
+    if last is not None:
+        # the DGLGraph step hands its result over in the node frame
+        out = last.pop()
+        dump_outputs(args.dump_outputs, {"h_out": g.ndata["h_out"] if out is None else out})
+        del out
     value = num_edges_total * args.steps / elapsed
     roof = roofline_block(
         num_local_edges, num_rows, kernel_ms, world, dev, n * FEAT * 4, blocks,
@@ -1207,7 +1279,7 @@ def main(argv=None):
     legs = LegRunner(result, world, rank, deadline, group=side_group)
     distributed = dist.is_initialized()
 
-    if distributed:
+    if distributed and args.full:
         legs.run("halo_exchange", lambda: None,
                  lambda _: exchange_block(pg, h_local, args.steps, world, dev))
     if distributed and args.halo_dtype == "fp32" and not args.no_bf16_leg:
@@ -1280,7 +1352,7 @@ def main(argv=None):
     if distributed and args.workload == "reddit" and not args.no_strong_leg:
         legs.run("strong", lambda: strong_setup(args, world, rank, dev),
                  lambda st: strong_run(args, world, rank, dev, st))
-    if sample is not None or world > 1:
+    if sample is not None or (world > 1 and args.full):
         # rank 0, after the timed region (the other ranks wait in agree)
         def cpu_run(_):
             if sample is None:

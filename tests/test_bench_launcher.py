@@ -2,8 +2,8 @@
 
 `python bench.py --gpus N` (N > 1, no WORLD_SIZE) must start N ranks itself as
 a child torchrun, relay rank 0's JSON line and exit with the child's code; an
-outer launcher whose WORLD_SIZE disagrees with --gpus is an error. The
-multi-rank line carries cpu_baseline, a per-rank rmat roofline and the
+outer launcher whose WORLD_SIZE disagrees with --gpus is an error. With
+`--full` the multi-rank line carries cpu_baseline, a per-rank rmat roofline and the
 halo_exchange block (VERDICT r02 "Next" 1). `--device cpu` runs the same
 plumbing through the library's host kernels.
 """
@@ -69,7 +69,8 @@ def test_bench_two_ranks_without_outer_launcher():
         env.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2",
                         "--device", "cpu", "--graph-scale", "0.002", "--rmat-scale", "12",
-                        "--steps", "2", "--warmup", "1", "--cpu-sample-edges", "20000"],
+                        "--steps", "2", "--warmup", "1", "--cpu-sample-edges", "20000",
+                        "--full"],
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
     assert p.returncode == 0, p.stderr.decode()[-3000:]
     # stdout holds rank 0's JSON line and nothing else (the gloo groups'
@@ -100,6 +101,60 @@ def test_bench_two_ranks_without_outer_launcher():
         bench.algorithmic_bytes(1 << 16, 0, bench.FEAT)
 
 
+_LEGS = ("one_launch", "train_step", "gcn_reddit", "gat", "sage", "gat_pubmed", "rgcn", "rmat12",
+         "sage_rmat12", "halo_exchange", "halo_bf16", "strong")
+
+
+def test_plain_run_is_the_headline_alone_and_dumps_its_output(tmp_path):
+    """Without --full: the line with its headline fields and no secondary leg;
+    --dump-outputs writes the last timed step's rows, the same from run to
+    run, and they are the step's (copy_u + sum of the seeded features)."""
+    import numpy as np
+    lines, outs = [], []
+    for d in ("a", "b"):
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1",
+                            "--device", "cpu", "--graph-scale", "0.002", "--rmat-scale", "12",
+                            "--steps", "3", "--warmup", "1",
+                            "--dump-outputs", str(tmp_path / d)],
+                           env=_bench_env(), stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                           timeout=300)
+        assert p.returncode == 0, p.stderr.decode()[-3000:]
+        lines.append(_line(p.stdout))
+        assert os.listdir(str(tmp_path / d)) == ["h_out.npy"]
+        outs.append(np.load(str(tmp_path / d / "h_out.npy")))
+    r = lines[0]
+    assert r["steps"] == 3 and r["warmup"] == 1 and r["ms_per_step"] > 0
+    assert r["unit"] == "edges/s" and r["higher_is_better"] is True and r["dtype"] == "fp32"
+    assert r["metric"] == "edges/sec on update_all g-SpMM (copy_u+sum, feat=128)"
+    edges = int(r["config"]["workload"].split(" nodes, ")[1].split(" edges")[0])
+    assert abs(r["value"] - edges / (r["ms_per_step"] * 1e-3)) <= 1e-6 * r["value"]
+    assert r["cpu_baseline"] is None and r["roofline"]["traffic"] is None
+    assert not [k for k in _LEGS if k in r]
+    assert outs[0].dtype == np.float32 and outs[0].shape == (r["config"]["global_batch"], 128)
+    assert np.array_equal(outs[0], outs[1])
+    assert np.isfinite(outs[0]).all() and np.abs(outs[0]).max() > 0
+
+
+def test_dump_outputs_samples_rows_within_the_budget(tmp_path, monkeypatch):
+    import numpy as np
+    import torch
+    monkeypatch.setattr(bench, "DUMP_BYTES", 4 * 8 * 10)  # ten fp32 rows of width 8
+    t = torch.arange(33 * 8, dtype=torch.float32).reshape(33, 8)
+    small = torch.arange(6, dtype=torch.float64).reshape(3, 2)
+    bench.dump_outputs(str(tmp_path / "x"), {"t": t})
+    bench.dump_outputs(str(tmp_path / "y"), {"t": t.clone(), "small": small})
+    a = np.load(str(tmp_path / "x" / "t.npy"))
+    b = np.load(str(tmp_path / "y" / "t.npy"))
+    assert a.shape == (10, 8) and a.dtype == np.float32
+    rows = (a[:, 0] / 8).astype(int)
+    assert (np.diff(rows) > 0).all() and np.array_equal(a, t.numpy()[rows])  # whole rows, in order
+    assert b.shape == (5, 8) and np.array_equal(b, t.numpy()[(b[:, 0] / 8).astype(int)])
+    s = np.load(str(tmp_path / "y" / "small.npy"))
+    assert s.dtype == np.float64 and np.array_equal(s, small.numpy())
+    total = sum(os.path.getsize(str(tmp_path / "y" / f)) - 128 for f in ("t.npy", "small.npy"))
+    assert total <= 4 * 8 * 10
+
+
 def _bench_env(**extra):
     env = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT",
@@ -110,7 +165,7 @@ def _bench_env(**extra):
 
 
 _SMALL = ["--gpus", "2", "--device", "cpu", "--graph-scale", "0.002", "--rmat-scale", "12",
-          "--steps", "2", "--warmup", "1", "--cpu-sample-edges", "20000"]
+          "--steps", "2", "--warmup", "1", "--cpu-sample-edges", "20000", "--full"]
 
 
 def _line(stdout):

@@ -3,6 +3,7 @@
 # Stops at the first step that faults / aborts / times out (exit >= 2 or 124/134/137/139).
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
+OUT=$_  # the output folder made above
 export HSA_ENABLE_IPC_MODE_LEGACY=0
 ok() { local rc=$1; [ "$rc" -eq 0 ] || [ "$rc" -eq 1 ]; }
 STEPS="${STEPS:-tests smoke bench prof}"
@@ -37,10 +38,10 @@ for s in $STEPS; do
       rc=$?; tail -3 gpurun_out/smoke.log; [ $rc -eq 0 ] || exit $rc ;;
     benchquick)
       # the default line's legs without the PMC passes and the RMAT leg
-      timeout -k 10 600 python bench.py --no-traffic --no-rmat-leg ${BENCH_ARGS:-} > gpurun_out/benchquick.json 2> gpurun_out/benchquick.err
+      timeout -k 10 600 python bench.py --full --no-traffic --no-rmat-leg ${BENCH_ARGS:-} > $OUT/benchquick.json 2> $OUT/benchquick.err
       rc=$?; tail -12 gpurun_out/benchquick.err; [ $rc -eq 0 ] || exit $rc ;;
     bench)
-      timeout -k 10 600 python bench.py > gpurun_out/bench.json 2> gpurun_out/bench.err
+      timeout -k 10 600 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
       rc=$?; tail -5 gpurun_out/bench.err; cat gpurun_out/bench.json; [ $rc -eq 0 ] || exit $rc ;;
     prof)
       # the bench line and the kernel statistics of the SAME process (headline leg only)
@@ -55,12 +56,12 @@ for s in $STEPS; do
     dist)
       # rehearse the multi-rank bench path: 2 ranks sharing the one GPU over gloo
       timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-        --master-addr 127.0.0.1 --master-port 29611 bench.py --gpus 2 --steps 3 --warmup 1 --rmat-scale 18 \
+        --master-addr 127.0.0.1 --master-port 29611 bench.py --full --gpus 2 --steps 3 --warmup 1 --rmat-scale 18 \
         --graph-scale 0.05 --dist-backend gloo > gpurun_out/dist.json 2> gpurun_out/dist.err
       rc=$?; tail -3 gpurun_out/dist.err; cat gpurun_out/dist.json; [ $rc -eq 0 ] || exit $rc ;;
     rehearsal)
       # the N>1 bench path (RCCL group, partition, collectives, max-over-ranks timing) on one rank
-      timeout -k 10 600 python bench.py --dist-rehearsal --no-traffic --steps 5 --warmup 2 \
+      timeout -k 10 600 python bench.py --full --dist-rehearsal --no-traffic --steps 5 --warmup 2 \
         > gpurun_out/rehearsal.json 2> gpurun_out/rehearsal.err
       rc=$?; tail -4 gpurun_out/rehearsal.err; cat gpurun_out/rehearsal.json; [ $rc -eq 0 ] || exit $rc ;;
     examples)
@@ -152,7 +153,7 @@ for s in $STEPS; do
       # one model leg under the kernel trace (LEG=gcn_reddit): its timed epochs' kernels alone
       cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
       timeout -k 10 600 rocprofv3 --kernel-trace --stats -d gpurun_out/legprof -o run \
-        --output-format csv -- python bench.py --no-traffic --no-rmat-leg --no-sage-rmat-leg \
+        --output-format csv -- python bench.py --full --no-traffic --no-rmat-leg --no-sage-rmat-leg \
         --no-train-leg --no-one-launch-leg --no-cpu-baseline --model-legs ${LEG:-gcn_reddit} \
         > gpurun_out/legprof.json 2> gpurun_out/legprof.log
       rc=$?; tail -1 gpurun_out/legprof.log; [ $rc -eq 0 ] || exit $rc
@@ -161,7 +162,7 @@ for s in $STEPS; do
     rgcnlegs)
       # the R-GCN leg alone, REPEAT times (process-to-process spread), then its host study
       for i in $(seq ${REPEAT:-3}); do
-        timeout -k 10 300 python bench.py --no-traffic --no-rmat-leg --no-sage-rmat-leg --no-train-leg \
+        timeout -k 10 300 python bench.py --full --no-traffic --no-rmat-leg --no-sage-rmat-leg --no-train-leg \
           --no-one-launch-leg --no-cpu-baseline --model-legs rgcn > gpurun_out/rgcn_leg_$i.json 2> gpurun_out/rgcn_leg_$i.err
         rc=$?; [ $rc -eq 0 ] || { tail -3 gpurun_out/rgcn_leg_$i.err; exit $rc; }
         python -c "import json; d=json.load(open('gpurun_out/rgcn_leg_$i.json'))['rgcn']; print('rgcn', d['ms_per_step'], d['kernel_ms'], d['launches_per_step'])"
@@ -185,7 +186,7 @@ for s in $STEPS; do
       rc=$?; tail -3 gpurun_out/gat_bwd_variants.log; [ $rc -eq 0 ] || exit $rc ;;
     benchlegs)
       # the N = 1 line without the PMC passes, the RMAT legs and the CPU baselines (model legs timed)
-      timeout -k 10 600 python bench.py --no-traffic --no-rmat-leg --no-sage-rmat-leg --no-cpu-baseline \
+      timeout -k 10 600 python bench.py --full --no-traffic --no-rmat-leg --no-sage-rmat-leg --no-cpu-baseline \
         ${BENCH_ARGS:-} > gpurun_out/benchlegs.json 2> gpurun_out/benchlegs.err
       rc=$?; tail -3 gpurun_out/benchlegs.err; [ $rc -eq 0 ] || exit $rc
       python tools/bench_summary.py gpurun_out/benchlegs.json ;;
