@@ -842,8 +842,8 @@ int dglhip_gat_aggregate_logits_ranges_device(
     // 6.49; one-float lanes level: Pubmed's 8 x 8 and 8 x 3;
     // tools/gat_early_ab.py); variant 2 keeps them after it, 3 before it
     const bool early = g_gat_variant == 3 || (g_gat_variant == 0 && v2);
-    if (num_heads == 8 && v2 && early && (g_row_pol == 2 || g_row_pol == 4)) {
-      // the running rows' cache policy (dglhip_set_row_policy) on the 8-head
+    if (num_heads == 8 && v2 && early) {
+      // the running rows' cache policy (RP 2: load_out / store_out) on the 8-head
       // two-float shape (the Reddit-shaped 8 x 16 layer); with attn_l the
       // sources' logits recomputed from their gathered rows (LOGIT)
       const bool logit = attn_l != nullptr && head_dim == 16 && g_gat_logit_on;
@@ -869,20 +869,17 @@ int dglhip_gat_aggregate_logits_ranges_device(
                      accumulate, indices, row_order, el, er, ft, alpha, clamp_lo, clamp_hi,      \
                      apply_exp, seed, seed_offset, thr, scale, out_ft, out_z, attn_out,          \
                      attn_drop_out, tbytes, nullptr)
-        if (g_row_pol == 2 && !logit && g_gat_fwd_waves == 6) {
+        if (!logit && g_gat_fwd_waves == 6) {
           // study knob: at least 6 waves per SIMD (the no-dropout kernel is 81
           // VGPRs, one over the 80 that 6 waves allow)
           if (drop) { if (small) DGLHIP_GATW(true, true, 6); else DGLHIP_GATW(true, false, 6); }
           else { if (small) DGLHIP_GATW(false, true, 6); else DGLHIP_GATW(false, false, 6); }
-        } else if (g_row_pol == 2 && !logit && g_gat_fwd_waves == 5) {
+        } else if (!logit && g_gat_fwd_waves == 5) {
           if (drop) { if (small) DGLHIP_GATW(true, true, 5); else DGLHIP_GATW(true, false, 5); }
           else { if (small) DGLHIP_GATW(false, true, 5); else DGLHIP_GATW(false, false, 5); }
-        } else if (g_row_pol == 2) {
+        } else {
           if (drop) { if (small) DGLHIP_GATRP(true, true, 2); else DGLHIP_GATRP(true, false, 2); }
           else { if (small) DGLHIP_GATRP(false, true, 2); else DGLHIP_GATRP(false, false, 2); }
-        } else {
-          if (drop) { if (small) DGLHIP_GATRP(true, true, 4); else DGLHIP_GATRP(true, false, 4); }
-          else { if (small) DGLHIP_GATRP(false, true, 4); else DGLHIP_GATRP(false, false, 4); }
         }
 #undef DGLHIP_GATRP
 #undef DGLHIP_GATW
@@ -996,12 +993,7 @@ static int gat_backward_t_impl(
     else if (w5) DGLHIP_GBT_W(DD, SM, RPV, 5, false);                                         \
     else DGLHIP_GBT_W(DD, SM, RPV, 4, false);                                                 \
   } while (0)
-#define DGLHIP_GBT(DD, SM)                                                                    \
-  do {                                                                                        \
-    if (g_row_pol == 2) DGLHIP_GBT_R(DD, SM, 2);                                              \
-    else if (g_row_pol == 4) DGLHIP_GBT_R(DD, SM, 4);                                         \
-    else DGLHIP_GBT_R(DD, SM, 0);                                                             \
-  } while (0)
+#define DGLHIP_GBT(DD, SM) DGLHIP_GBT_R(DD, SM, 2)  // the running rows' cache policy: RP 2
     if (drop) {
       if (small) DGLHIP_GBT(true, true); else DGLHIP_GBT(true, false);
     } else {

@@ -21,8 +21,6 @@
 //  * Rows are launched in degree-descending order (row_order) so the longest
 //    sequential chains start first and the tail is short.
 
-#include <cstdlib>
-
 #include "gspmm_impl.h"
 
 namespace dglhip {
@@ -443,176 +441,61 @@ __global__ __launch_bounds__(256) void gsddmm_attention_vec_kernel(
 
 // definitions of the state gspmm_impl.h declares
 Timing g_timing;
-int g_var_vec = 0, g_var_group = 0, g_var_unroll = 0, g_var_pipe = 0;
-int g_cache_policy = -1;
-int g_gather_buf = 2;
-// running rows of the blocked launches: non-temporal loads, sc1 stores (the
-// line leaves the XCD's L2): Reddit-shaped headline 3.83 -> 3.74 ms, GAT 8 x 16
-// forward + backward 17.01 -> 16.94 (tools/rowpol_ab.py, profiles/r04/rowpol_ab.json)
-int g_row_pol = 2;
 int g_sddmm_alt = 0;
 
-// ---------------------------------------------------------------------------
-// Narrow rows, two slots per gather (r06): copy_u + sum over the blocked
-// schedule's items when a source row is at most 64 floats (F = 41 at its
-// 48-float padded stride: GCN's output layer). The one-row-per-wave kernel
-// gathers such a row with 48 of 64 lanes one slot per instruction; here the
-// wave's halves gather consecutive slots k and k + 1 of the same item (lane
-// 32h + j holds floats 2j, 2j + 1 of slot k + h), and the lower half adds
-// them in slot order: acc = (acc + s_k) + s_{k+1}, the second operand brought
-// down through the LDS crossbar (ds_bpermute). Every output element is the one-launch kernel's
-// chain (same additions, same order), so the bits are unchanged; the gather
-// instructions per slot halve. The column ids stay scalar (both slots' ids
-// through the scalar cache, a select per half), the rows are read through one
-// buffer descriptor over the whole table (32-bit lane offsets).
-// ---------------------------------------------------------------------------
-int g_pair_slots = [] {
-  const char* e = std::getenv("DGLHIP_PAIR_SLOTS");
-  return e ? std::atoi(e) : 0;
-}();
-
-__device__ __forceinline__ float upper_half(float v, int from) {
-  // lanes 0..31 receive lanes 32..63's values (ds_bpermute: the LDS
-  // crossbar, no LDS storage; ``from`` = the source lane's byte address)
-  return __int_as_float(__builtin_amdgcn_ds_bpermute(from, __float_as_int(v)));
-}
-
-// VEC floats per lane (2: rows of <= 64 floats; 4: rows of <= 128, the
-// headline's F = 128, 16-B gathers); RP: the running rows' cache policy of
-// the one-slot kernel (load_out / store_out: non-temporal loads, sc1 stores
-// by default), so the two kernels treat the blocked schedule's passes alike.
-template <int VEC, int UNROLL, bool ACCUM, int RP>
-__global__ __launch_bounds__(256) void gspmm_pair_items_kernel(
-    int64_t num_items, int64_t F, int64_t ld, int64_t table_bytes,
-    const int32_t* __restrict__ item_rows, const int64_t* __restrict__ item_ptr,
-    const int32_t* __restrict__ indices, const float* __restrict__ ufeat,
-    float* __restrict__ out) {
-  typedef typename Vec<VEC>::T V;
-  typedef unsigned int uvec __attribute__((ext_vector_type(VEC)));
-  const int64_t it = block_linear() * 4 +
-                     __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
-  if (it >= num_items) return;
-  const int lane = threadIdx.x & 63, half = lane >> 5;
-  const int64_t f0 = int64_t(lane & 31) * VEC;
-  const bool active = f0 < F;  // the lane's last floats may be row padding (ld > F)
-  const bool in_row = f0 < ld;  // lanes past the row read nothing (no next-row lines)
-  auto uni64 = [](int64_t x) {  // a wave-uniform 64-bit value, said so
-    return int64_t((uint64_t(uint32_t(__builtin_amdgcn_readfirstlane(int32_t(x >> 32)))) << 32) |
-                   uint32_t(__builtin_amdgcn_readfirstlane(int32_t(x))));
-  };
-  const int64_t row = __builtin_amdgcn_readfirstlane(item_rows[it]);
-  const int64_t beg = uni64(item_ptr[it]), end = uni64(item_ptr[it + 1]);
-  const __amdgpu_buffer_rsrc_t tab = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(ufeat), 0, static_cast<int>(table_bytes), 0x00020000);
-  const uint32_t foff = static_cast<uint32_t>(f0 * 4);
-  const uint32_t rowb = static_cast<uint32_t>(ld * 4);
-  const int from = ((lane + 32) & 63) * 4;
-  float* orow = out + row * F;
-  // whole-vector running rows where the row holds them (F a multiple of VEC)
-  const bool vec_out = F % VEC == 0;
-  float a[VEC];
-  if (ACCUM && half == 0 && active && vec_out) {
-    const V v = load_out<VEC, RP>(orow, f0);
-#pragma unroll
-    for (int c = 0; c < VEC; ++c) a[c] = v[c];
+// The (message, edge layout) pair of a launch: the twelve pairs the sum/mean
+// and max reducers are instantiated for (gspmm_inst.hip).
+template <class... Args>
+static void dispatch_msg_layout(int msg_op, int em, const Args&... args) {
+  if (msg_op == DGLHIP_MSG_COPY_U_BF16) {
+    dispatch_me<DGLHIP_MSG_COPY_U_BF16, EM_SCALAR>(args...);
+  } else if (msg_op == DGLHIP_MSG_COPY_U) {
+    dispatch_me<DGLHIP_MSG_COPY_U, EM_SCALAR>(args...);
+  } else if (msg_op == DGLHIP_MSG_U_MUL_E) {
+    if (em == EM_FULL) dispatch_me<DGLHIP_MSG_U_MUL_E, EM_FULL>(args...);
+    else if (em == EM_SCALAR) dispatch_me<DGLHIP_MSG_U_MUL_E, EM_SCALAR>(args...);
+    else dispatch_me<DGLHIP_MSG_U_MUL_E, EM_HEAD>(args...);
   } else {
-#pragma unroll
-    for (int c = 0; c < VEC; ++c) a[c] = (ACCUM && half == 0 && f0 + c < F) ? orow[f0 + c] : 0.0f;
+    if (em == EM_FULL) dispatch_me<DGLHIP_MSG_COPY_E, EM_FULL>(args...);
+    else if (em == EM_SCALAR) dispatch_me<DGLHIP_MSG_COPY_E, EM_SCALAR>(args...);
+    else dispatch_me<DGLHIP_MSG_COPY_E, EM_HEAD>(args...);
   }
-  // one loop for full and partial batches: rem is wave-uniform, so the
-  // predicates are scalar branches (a separate predicated tail batch doubled
-  // the live registers: 126 against 42 VGPRs at VEC 2)
-  for (int64_t k = beg; k < end; k += 2 * UNROLL) {
-    const int64_t rem = end - k;
-    float v[UNROLL][VEC];
-#pragma unroll
-    for (int j = 0; j < UNROLL; ++j) {
-      if (2 * j < rem) {
-        const int32_t ca = indices[k + 2 * j];
-        const int32_t cb = 2 * j + 1 < rem ? indices[k + 2 * j + 1] : ca;
-        const uint32_t off = static_cast<uint32_t>(half ? cb : ca) * rowb + foff;
-        uvec w = uvec(0u);
-        if (in_row) {
-          if constexpr (VEC == 4) w = __builtin_amdgcn_raw_buffer_load_b128(tab, off, 0, 0);
-          else w = __builtin_amdgcn_raw_buffer_load_b64(tab, off, 0, 0);
-        }
-#pragma unroll
-        for (int c = 0; c < VEC; ++c) v[j][c] = __uint_as_float(w[c]);
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < UNROLL; ++j) {
-      if (2 * j < rem) {
-        float w[VEC];
-#pragma unroll
-        for (int c = 0; c < VEC; ++c) w[c] = upper_half(v[j][c], from);
-#pragma unroll
-        for (int c = 0; c < VEC; ++c) a[c] += v[j][c];  // slot k + 2j (this half's own)
-        if (2 * j + 1 < rem) {                           // then slot k + 2j + 1
-#pragma unroll
-          for (int c = 0; c < VEC; ++c) a[c] += w[c];
-        }
-      }
-    }
-  }
-  if (half == 0 && active) {
-    if (vec_out) {
-      V v;
-#pragma unroll
-      for (int c = 0; c < VEC; ++c) v[c] = a[c];
-      store_out<VEC, RP>(orow, f0, v);
-    } else {
-#pragma unroll
-      for (int c = 0; c < VEC; ++c)
-        if (f0 + c < F) orow[f0 + c] = a[c];
-    }
-  }
-}
-
-// the paired kernel's shapes: copy_u, rows of <= 64 floats at an even stride,
-// a table the 32-bit buffer offsets span
-static int pair_vec(int64_t F, int64_t ld) {
-  if (F >= 16 && ld <= 64 && ld % 2 == 0) return 2;
-  return 0;
-}
-
-static bool pair_items_ok(int msg_op, int64_t F, int64_t ld, int64_t num_src_bytes) {
-  return g_pair_slots && msg_op == DGLHIP_MSG_COPY_U && pair_vec(F, ld) != 0 &&
-         num_src_bytes > 0 && num_src_bytes < (int64_t(1) << 31);
 }
 
 static void dispatch_sum(int msg_op, bool mean, const SumLaunch& a, hipStream_t stream) {
-  const int em = edge_mode(a.elen, a.F);
-  if (msg_op == DGLHIP_MSG_COPY_U_BF16) {
-    dispatch_sum_me<DGLHIP_MSG_COPY_U_BF16, EM_SCALAR>(mean, a, stream);
-  } else if (msg_op == DGLHIP_MSG_COPY_U) {
-    dispatch_sum_me<DGLHIP_MSG_COPY_U, EM_SCALAR>(mean, a, stream);
-  } else if (msg_op == DGLHIP_MSG_U_MUL_E) {
-    if (em == EM_FULL) dispatch_sum_me<DGLHIP_MSG_U_MUL_E, EM_FULL>(mean, a, stream);
-    else if (em == EM_SCALAR) dispatch_sum_me<DGLHIP_MSG_U_MUL_E, EM_SCALAR>(mean, a, stream);
-    else dispatch_sum_me<DGLHIP_MSG_U_MUL_E, EM_HEAD>(mean, a, stream);
-  } else {
-    if (em == EM_FULL) dispatch_sum_me<DGLHIP_MSG_COPY_E, EM_FULL>(mean, a, stream);
-    else if (em == EM_SCALAR) dispatch_sum_me<DGLHIP_MSG_COPY_E, EM_SCALAR>(mean, a, stream);
-    else dispatch_sum_me<DGLHIP_MSG_COPY_E, EM_HEAD>(mean, a, stream);
-  }
+  dispatch_msg_layout(msg_op, edge_mode(a.elen, a.F), mean, a, stream);
 }
 
 static void dispatch_max(int msg_op, const MaxLaunch& a, hipStream_t stream) {
-  const int em = edge_mode(a.elen, a.F);
-  if (msg_op == DGLHIP_MSG_COPY_U_BF16) {
-    dispatch_max_me<DGLHIP_MSG_COPY_U_BF16, EM_SCALAR>(a, stream);
-  } else if (msg_op == DGLHIP_MSG_COPY_U) {
-    dispatch_max_me<DGLHIP_MSG_COPY_U, EM_SCALAR>(a, stream);
-  } else if (msg_op == DGLHIP_MSG_U_MUL_E) {
-    if (em == EM_FULL) dispatch_max_me<DGLHIP_MSG_U_MUL_E, EM_FULL>(a, stream);
-    else if (em == EM_SCALAR) dispatch_max_me<DGLHIP_MSG_U_MUL_E, EM_SCALAR>(a, stream);
-    else dispatch_max_me<DGLHIP_MSG_U_MUL_E, EM_HEAD>(a, stream);
-  } else {
-    if (em == EM_FULL) dispatch_max_me<DGLHIP_MSG_COPY_E, EM_FULL>(a, stream);
-    else if (em == EM_SCALAR) dispatch_max_me<DGLHIP_MSG_COPY_E, EM_SCALAR>(a, stream);
-    else dispatch_max_me<DGLHIP_MSG_COPY_E, EM_HEAD>(a, stream);
-  }
+  dispatch_msg_layout(msg_op, edge_mode(a.elen, a.F), a, stream);
+}
+
+static bool is_mean(int reduce_op) {
+  return reduce_op == DGLHIP_REDUCE_MEAN || reduce_op == DGLHIP_REDUCE_MEAN_ACCUM;
+}
+
+static bool is_accum(int reduce_op) {
+  return reduce_op == DGLHIP_REDUCE_SUM_ACCUM || reduce_op == DGLHIP_REDUCE_MEAN_ACCUM;
+}
+
+// The operand checks of every g-SpMM entry point: the tables the message
+// reads are given, and an edge-feature row divides the feature row. Returns
+// the edge-feature length the kernels take (1 where the message reads none).
+static int64_t check_operands(int msg_op, int64_t feat_len, const float* ufeat,
+                              const float* efeat, int64_t efeat_len) {
+  const bool use_u = msg_op != DGLHIP_MSG_COPY_E;
+  const bool use_e = !copies_u(msg_op);
+  DGLHIP_CHECK(!use_u || ufeat, "ufeat is null");
+  DGLHIP_CHECK(!use_e || efeat, "efeat is null");
+  DGLHIP_CHECK(!use_e || (efeat_len >= 1 && feat_len % efeat_len == 0),
+               "edge feature length " << efeat_len << " must divide feat_len " << feat_len);
+  return use_e ? efeat_len : 1;
+}
+
+// a lane's vector of VEC features must not straddle padded rows: even strides only
+static void check_ufeat_ld(int64_t ufeat_ld, int64_t feat_len) {
+  DGLHIP_CHECK(ufeat_ld == 0 || ufeat_ld == feat_len || (ufeat_ld > feat_len && ufeat_ld % 2 == 0),
+               "ufeat_ld " << ufeat_ld << ": 0, feat_len, or an even width > feat_len");
 }
 
 }  // namespace dglhip
@@ -634,25 +517,16 @@ int dglhip_gspmm_device(int msg_op, int reduce_op, int64_t num_rows,
   DGLHIP_CHECK(num_rows >= 0 && feat_len >= 0, "negative size");
   if (num_rows == 0 || feat_len == 0) return 0;  // empty tensors may carry null pointers
   DGLHIP_CHECK(indptr != nullptr && out != nullptr, "null indptr/out");
-  const bool use_u = msg_op != DGLHIP_MSG_COPY_E;
-  const bool use_e = !copies_u(msg_op);
-  DGLHIP_CHECK(!use_u || ufeat, "ufeat is null");
-  DGLHIP_CHECK(!use_e || efeat, "efeat is null");
-  DGLHIP_CHECK(!use_e || (efeat_len >= 1 && feat_len % efeat_len == 0),
-               "edge feature length " << efeat_len << " must divide feat_len " << feat_len);
-  const int64_t elen = use_e ? efeat_len : 1;
+  const int64_t elen = check_operands(msg_op, feat_len, ufeat, efeat, efeat_len);
   if (reduce_op == DGLHIP_REDUCE_MAX) {
     MaxLaunch m{num_rows, feat_len, elen, indptr, indices, eid, ufeat, efeat, out, arg_out,
                 row_order};
     dispatch_max(msg_op, m, stream);
     return 0;
   }
-  const bool mean = reduce_op == DGLHIP_REDUCE_MEAN || reduce_op == DGLHIP_REDUCE_MEAN_ACCUM;
   SumLaunch a{num_rows, feat_len, elen, indptr, indices, eid, ufeat, efeat, out, row_order,
-              nullptr, nullptr,
-              reduce_op == DGLHIP_REDUCE_SUM_ACCUM || reduce_op == DGLHIP_REDUCE_MEAN_ACCUM,
-              stream_output(num_rows, feat_len)};
-  dispatch_sum(msg_op, mean, a, stream);
+              nullptr, nullptr, is_accum(reduce_op), stream_output(num_rows, feat_len)};
+  dispatch_sum(msg_op, is_mean(reduce_op), a, stream);
   API_END();
 }
 
@@ -672,18 +546,12 @@ int dglhip_gspmm_strided_device(int msg_op, int reduce_op, int64_t num_rows,
   DGLHIP_CHECK(ufeat_ld >= feat_len, "ufeat_ld " << ufeat_ld << " < feat_len " << feat_len);
   if (num_rows == 0 || feat_len == 0) return 0;
   DGLHIP_CHECK(indptr && out && ufeat, "null indptr/out/ufeat");
-  const bool use_e = msg_op == DGLHIP_MSG_U_MUL_E;
-  DGLHIP_CHECK(!use_e || efeat, "efeat is null");
-  DGLHIP_CHECK(!use_e || (efeat_len >= 1 && feat_len % efeat_len == 0),
-               "edge feature length " << efeat_len << " must divide feat_len " << feat_len);
+  const int64_t elen = check_operands(msg_op, feat_len, ufeat, efeat, efeat_len);
   // a lane's vector of VEC features must not straddle padded rows: even strides only
   DGLHIP_CHECK(ufeat_ld == feat_len || ufeat_ld % 2 == 0, "odd padded stride " << ufeat_ld);
-  SumLaunch a{num_rows, feat_len, use_e ? efeat_len : 1, indptr, indices, eid, ufeat, efeat, out,
-              row_order, nullptr, nullptr,
-              reduce_op == DGLHIP_REDUCE_SUM_ACCUM || reduce_op == DGLHIP_REDUCE_MEAN_ACCUM,
-              stream_output(num_rows, feat_len), ufeat_ld};
-  dispatch_sum(msg_op, reduce_op == DGLHIP_REDUCE_MEAN || reduce_op == DGLHIP_REDUCE_MEAN_ACCUM,
-               a, stream);
+  SumLaunch a{num_rows, feat_len, elen, indptr, indices, eid, ufeat, efeat, out, row_order,
+              nullptr, nullptr, is_accum(reduce_op), stream_output(num_rows, feat_len), ufeat_ld};
+  dispatch_sum(msg_op, is_mean(reduce_op), a, stream);
   API_END();
 }
 
@@ -705,21 +573,13 @@ int dglhip_gspmm_chunked_device(int msg_op, int reduce_op, int64_t feat_len,
                "chunked rows support sum/mean only");
   DGLHIP_CHECK(num_light >= 0 && num_chunks >= 0 && num_heavy >= 0, "negative size");
   if (feat_len == 0) return 0;
-  const bool use_u = msg_op != DGLHIP_MSG_COPY_E;
-  const bool use_e = !copies_u(msg_op);
-  DGLHIP_CHECK(!use_u || ufeat, "ufeat is null");
-  DGLHIP_CHECK(!use_e || efeat, "efeat is null");
-  DGLHIP_CHECK(!use_e || (efeat_len >= 1 && feat_len % efeat_len == 0),
-               "edge feature length " << efeat_len << " must divide feat_len " << feat_len);
+  const int64_t elen = check_operands(msg_op, feat_len, ufeat, efeat, efeat_len);
   DGLHIP_CHECK(num_chunks == 0 || (partial && chunk_beg && chunk_end), "null chunk plan");
-  DGLHIP_CHECK(ufeat_ld == 0 || ufeat_ld == feat_len || (ufeat_ld > feat_len && ufeat_ld % 2 == 0),
-               "ufeat_ld " << ufeat_ld << ": 0, feat_len, or an even width > feat_len");
+  check_ufeat_ld(ufeat_ld, feat_len);
   DGLHIP_CHECK(ufeat_ld == 0 || ufeat_ld == feat_len || msg_op == DGLHIP_MSG_COPY_U ||
                    msg_op == DGLHIP_MSG_U_MUL_E,
                "strided source rows: copy_u or u_mul_e, got msg op " << msg_op);
-  const int64_t elen = use_e ? efeat_len : 1;
-  const bool mean = reduce_op == DGLHIP_REDUCE_MEAN || reduce_op == DGLHIP_REDUCE_MEAN_ACCUM;
-  const bool accum = reduce_op == DGLHIP_REDUCE_SUM_ACCUM || reduce_op == DGLHIP_REDUCE_MEAN_ACCUM;
+  const bool mean = is_mean(reduce_op), accum = is_accum(reduce_op);
   if (num_chunks > 0) {  // heavy-row chunks first: the longest work starts first
     SumLaunch c{num_chunks, feat_len, elen, indptr, indices, eid, ufeat, efeat, partial,
                 nullptr, chunk_beg, chunk_end, false, false, ufeat_ld};
@@ -733,27 +593,11 @@ int dglhip_gspmm_chunked_device(int msg_op, int reduce_op, int64_t feat_len,
   }
   if (num_heavy > 0) {
     const int64_t blocks = (num_heavy + 3) / 4;
+    auto combine = mean ? (accum ? gspmm_combine_kernel<true, true> : gspmm_combine_kernel<true, false>)
+                        : (accum ? gspmm_combine_kernel<false, true> : gspmm_combine_kernel<false, false>);
     timed_launch(stream, [&] {
-      if (mean && accum)
-        hipLaunchKernelGGL((gspmm_combine_kernel<true, true>),
-                           grid_1d(blocks), dim3(256), 0, stream,
-                           num_heavy, feat_len, indptr, heavy_rows, heavy_chunk_ptr, partial,
-                           out);
-      else if (mean)
-        hipLaunchKernelGGL((gspmm_combine_kernel<true, false>),
-                           grid_1d(blocks), dim3(256), 0, stream,
-                           num_heavy, feat_len, indptr, heavy_rows, heavy_chunk_ptr, partial,
-                           out);
-      else if (accum)
-        hipLaunchKernelGGL((gspmm_combine_kernel<false, true>),
-                           grid_1d(blocks), dim3(256), 0, stream,
-                           num_heavy, feat_len, indptr, heavy_rows, heavy_chunk_ptr, partial,
-                           out);
-      else
-        hipLaunchKernelGGL((gspmm_combine_kernel<false, false>),
-                           grid_1d(blocks), dim3(256), 0, stream,
-                           num_heavy, feat_len, indptr, heavy_rows, heavy_chunk_ptr, partial,
-                           out);
+      hipLaunchKernelGGL(combine, grid_1d(blocks), dim3(256), 0, stream, num_heavy, feat_len,
+                         indptr, heavy_rows, heavy_chunk_ptr, partial, out);
     });
   }
   API_END();
@@ -769,65 +613,13 @@ int dglhip_gspmm_items_device(int msg_op, int64_t num_items, int64_t feat_len,
   DGLHIP_CHECK(msg_op >= 0 && msg_op <= 3, "unknown msg op " << msg_op);
   DGLHIP_CHECK(num_items >= 0 && feat_len >= 0, "negative size");
   if (num_items == 0 || feat_len == 0) return 0;
-  const bool use_u = msg_op != DGLHIP_MSG_COPY_E;
-  const bool use_e = !copies_u(msg_op);
   DGLHIP_CHECK(item_rows && item_ptr && indices && out, "null items/indices/out");
-  DGLHIP_CHECK(!use_u || ufeat, "ufeat is null");
-  DGLHIP_CHECK(!use_e || efeat, "efeat is null");
-  DGLHIP_CHECK(!use_e || (efeat_len >= 1 && feat_len % efeat_len == 0),
-               "edge feature length " << efeat_len << " must divide feat_len " << feat_len);
-  DGLHIP_CHECK(ufeat_ld == 0 || ufeat_ld == feat_len || (ufeat_ld > feat_len && ufeat_ld % 2 == 0),
-               "ufeat_ld " << ufeat_ld << ": 0, feat_len, or an even width > feat_len");
-  SumLaunch a{num_items, feat_len, use_e ? efeat_len : 1, nullptr, indices, eid, ufeat, efeat,
+  const int64_t elen = check_operands(msg_op, feat_len, ufeat, efeat, efeat_len);
+  check_ufeat_ld(ufeat_ld, feat_len);
+  SumLaunch a{num_items, feat_len, elen, nullptr, indices, eid, ufeat, efeat,
               out, item_rows, item_ptr, item_ptr + 1, accumulate != 0, false, ufeat_ld};
   dispatch_sum(msg_op, false, a, stream);
   API_END();
-}
-
-int dglhip_gspmm_pair_items_ok(int msg_op, int64_t feat_len, int64_t ufeat_ld,
-                               int64_t num_src_rows) {
-  const int64_t ld = ufeat_ld ? ufeat_ld : feat_len;
-  return pair_items_ok(msg_op, feat_len, ld, num_src_rows * ld * 4) ? 1 : 0;
-}
-
-int dglhip_gspmm_pair_items_device(int64_t num_items, int64_t feat_len, int64_t ufeat_ld,
-                                   int64_t num_src_rows, const int32_t* item_rows,
-                                   const int64_t* item_ptr, int accumulate,
-                                   const int32_t* indices, const float* ufeat, float* out,
-                                   void* stream_) {
-  API_BEGIN();
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  const int64_t ld = ufeat_ld ? ufeat_ld : feat_len;
-  DGLHIP_CHECK(num_items >= 0 && feat_len >= 0 && num_src_rows >= 0, "negative size");
-  DGLHIP_CHECK(pair_items_ok(DGLHIP_MSG_COPY_U, feat_len, ld, num_src_rows * ld * 4),
-               "paired gathers take copy_u rows of 16..64 floats at an even stride <= 64 "
-               "over a table under 2 GiB (F " << feat_len << ", stride " << ld << ")");
-  if (num_items == 0 || feat_len == 0) return 0;
-  DGLHIP_CHECK(item_rows && item_ptr && indices && ufeat && out, "null argument");
-  const dim3 grid = grid_1d((num_items + 3) / 4);
-  const int64_t bytes = num_src_rows * ld * 4;
-  // 32 slots (16 gathers) in flight per wave at VEC 2; 16 slots (8 gathers
-  // of 16 B: 44 VGPRs, where 16 took 76) at VEC 4, the one-slot kernel's 16
-#define DGLHIP_PAIR(VEC, ACC, RPV)                                                            \
-  hipLaunchKernelGGL((gspmm_pair_items_kernel<VEC, VEC == 4 ? 8 : 16, ACC, RPV>), grid,       \
-                     dim3(256), 0, stream, num_items, feat_len, ld, bytes, item_rows,         \
-                     item_ptr, indices, ufeat, out)
-  const int vec = pair_vec(feat_len, ld);
-  timed_launch(stream, [&] {
-    // the running rows as the one-slot kernel treats them (g_row_pol; the
-    // first launch only stores: sc1, as policy 4)
-    (void)vec;  // 2: rows of <= 64 floats (a VEC 4 form for 128-float rows measured
-                // 4.58 vs 3.75 ms on the headline and was dropped)
-    if (accumulate) DGLHIP_PAIR(2, true, 0);
-    else DGLHIP_PAIR(2, false, 0);
-  });
-#undef DGLHIP_PAIR
-  API_END();
-}
-
-int dglhip_set_pair_slots(int on) {
-  g_pair_slots = on ? 1 : 0;
-  return 0;
 }
 
 int dglhip_gspmm_max_ranges_device(int msg_op, int64_t num_rows, int64_t feat_len,
@@ -843,13 +635,8 @@ int dglhip_gspmm_max_ranges_device(int msg_op, int64_t num_rows, int64_t feat_le
   DGLHIP_CHECK(num_rows >= 0 && feat_len >= 0, "negative size");
   if (num_rows == 0 || feat_len == 0) return 0;
   DGLHIP_CHECK(indptr && row_beg && row_end && out, "null indptr/ranges/out");
-  const bool use_u = msg_op != DGLHIP_MSG_COPY_E;
-  const bool use_e = !copies_u(msg_op);
-  DGLHIP_CHECK(!use_u || ufeat, "ufeat is null");
-  DGLHIP_CHECK(!use_e || efeat, "efeat is null");
-  DGLHIP_CHECK(!use_e || (efeat_len >= 1 && feat_len % efeat_len == 0),
-               "edge feature length " << efeat_len << " must divide feat_len " << feat_len);
-  MaxLaunch m{num_rows, feat_len, use_e ? efeat_len : 1, indptr, indices, eid, ufeat, efeat,
+  const int64_t elen = check_operands(msg_op, feat_len, ufeat, efeat, efeat_len);
+  MaxLaunch m{num_rows, feat_len, elen, indptr, indices, eid, ufeat, efeat,
               out, arg_out, row_order, row_beg, row_end, accumulate != 0 ? 1 : 0};
   dispatch_max(msg_op, m, stream);
   API_END();
@@ -865,14 +652,9 @@ int dglhip_gspmm_ranges_device(int msg_op, int64_t num_items, int64_t feat_len,
   DGLHIP_CHECK(msg_op >= 0 && msg_op <= 3, "unknown msg op " << msg_op);
   DGLHIP_CHECK(num_items >= 0 && feat_len >= 0, "negative size");
   if (num_items == 0 || feat_len == 0) return 0;
-  const bool use_u = msg_op != DGLHIP_MSG_COPY_E;
-  const bool use_e = !copies_u(msg_op);
   DGLHIP_CHECK(item_beg && item_end && out, "null ranges/out");
-  DGLHIP_CHECK(!use_u || ufeat, "ufeat is null");
-  DGLHIP_CHECK(!use_e || efeat, "efeat is null");
-  DGLHIP_CHECK(!use_e || (efeat_len >= 1 && feat_len % efeat_len == 0),
-               "edge feature length " << efeat_len << " must divide feat_len " << feat_len);
-  SumLaunch a{num_items, feat_len, use_e ? efeat_len : 1, nullptr, indices, eid, ufeat, efeat,
+  const int64_t elen = check_operands(msg_op, feat_len, ufeat, efeat, efeat_len);
+  SumLaunch a{num_items, feat_len, elen, nullptr, indices, eid, ufeat, efeat,
               out, nullptr, item_beg, item_end, accumulate != 0,
               stream_output(num_items, feat_len)};
   dispatch_sum(msg_op, false, a, stream);
@@ -1113,47 +895,12 @@ int dglhip_gat_attention_grad_device(int64_t num_rows, int64_t feat_len, int64_t
       attn, attn_drop, dz, alpha, clamp_lo, clamp_hi, apply_exp, drop_scale, grad, stream);
 }
 
-int dglhip_set_spmm_variant(int vec, int group, int unroll, int pipelined) {
-  API_BEGIN();
-  DGLHIP_CHECK((vec == 0) || ((vec == 1 || vec == 2 || vec == 4) &&
-                              (group == 32 || group == 64) &&
-                              (unroll == 4 || unroll == 8 || unroll == 16 || unroll == 32)),
-               "unsupported variant " << vec << "," << group << "," << unroll);
-  g_var_vec = vec;
-  g_var_group = group;
-  g_var_unroll = unroll;
-  g_var_pipe = pipelined ? 1 : 0;
-  API_END();
-}
-
 int dglhip_set_sddmm_variant(int alternate) {
   API_BEGIN();
   // bit 0: the other depth of slots in flight; bit 1: the GAT epilogue's
   // operands loaded after the dot product (the form before r03's prefetch)
   DGLHIP_CHECK(alternate >= 0 && alternate <= 3, "unsupported g-SDDMM variant " << alternate);
   g_sddmm_alt = alternate;
-  API_END();
-}
-
-int dglhip_set_gather_mode(int buffer_descriptors) {
-  API_BEGIN();
-  DGLHIP_CHECK(buffer_descriptors >= 0 && buffer_descriptors <= 3,
-               "unknown gather mode " << buffer_descriptors);
-  g_gather_buf = buffer_descriptors;
-  API_END();
-}
-
-int dglhip_set_row_policy(int policy) {
-  API_BEGIN();
-  DGLHIP_CHECK(policy >= 0 && policy <= 4, "unknown running-row policy " << policy);
-  g_row_pol = policy;
-  API_END();
-}
-
-int dglhip_set_cache_policy(int policy) {
-  API_BEGIN();
-  DGLHIP_CHECK(policy >= -1 && policy <= POL_NT_OUT, "unknown cache policy " << policy);
-  g_cache_policy = policy;
   API_END();
 }
 

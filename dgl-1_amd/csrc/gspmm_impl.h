@@ -1,6 +1,6 @@
 // Shared part of the g-SpMM kernels (sum / mean / max, every message and
 // edge-feature layout) and their launch logic. Included by gspmm.hip (the
-// C-ABI, which only declares dispatch_sum_me / dispatch_max_me) and by
+// C-ABI, which only declares the two dispatch_me overloads) and by
 // gspmm_inst.hip, which is compiled once per (message, edge layout) pair
 // (-DGSPMM_INST_MSG / -DGSPMM_INST_EM, see the Makefile) and instantiates
 // them, so the kernel variants build in parallel translation units.
@@ -120,16 +120,13 @@ __device__ __forceinline__ f32x4 gather_bf16<4>(const float* ufeat, int32_t col,
                __uint_as_float(w.y << 16), __uint_as_float(w.y & 0xffff0000u)};
 }
 
-// Cache policy of the source-row gathers and output stores (POL template
-// parameter; copy_u + sum at VEC 2 x 64 lanes, selected by dglhip_set_cache_policy):
+// Cache policy of the output stores (POL template parameter; copy_u + sum at
+// VEC 2 x 64 lanes, see stream_output):
 //  POL_DEFAULT : default policy everywhere.
-//  POL_NT      : every gather and the output store non-temporal.
-//  POL_HOT     : column ids carry a "hot source" flag in bit 31 (set by the host on
-//                the sources with the most out-edges); hot rows load with the
-//                default policy, all other rows and the output non-temporal, so
-//                once-read traffic does not evict the rows that are read again.
-//  POL_NT_OUT  : only the output store non-temporal.
-enum { POL_DEFAULT = 0, POL_NT = 1, POL_HOT = 2, POL_NT_OUT = 3 };
+//  POL_NT_OUT  : the output store non-temporal.
+// (Non-temporal gathers, and gathers non-temporal for all but flagged "hot"
+// source rows, were measured and removed: DESIGN.md, the r01 cache-policy study.)
+enum { POL_DEFAULT = 0, POL_NT_OUT = 3 };
 
 // BUF: the row is wave-uniform (a whole wave per row, the column id from the
 // scalar slot stream): gather it through a buffer descriptor built from the
@@ -157,23 +154,14 @@ __device__ __forceinline__ typename Vec<VEC>::T gather_row_buf(const float* row,
   return *reinterpret_cast<const V*>(&w);
 }
 
-template <int VEC, int POL, bool BUF = false>
+template <int VEC, bool BUF>
 __device__ __forceinline__ typename Vec<VEC>::T gather_row(const float* __restrict__ ufeat,
                                                            int32_t col, int64_t F, int64_t f0) {
-  typedef typename Vec<VEC>::T V;
-  if (BUF && (POL == POL_DEFAULT || POL == POL_NT_OUT))
-    return gather_row_buf<VEC>(ufeat + int64_t(col) * F, F, f0);
-  if (POL == POL_NT) {
-    return __builtin_nontemporal_load(reinterpret_cast<const V*>(ufeat + int64_t(col) * F + f0));
-  } else if (POL == POL_HOT) {
-    const V* p = reinterpret_cast<const V*>(ufeat + int64_t(col & 0x7fffffff) * F + f0);
-    if (col < 0) return *p;  // wave-uniform: col comes from the scalar slot stream
-    return __builtin_nontemporal_load(p);
-  }
+  if (BUF) return gather_row_buf<VEC>(ufeat + int64_t(col) * F, F, f0);
   return ldv<VEC>(ufeat + int64_t(col) * F + f0);
 }
 
-// Output rows: non-temporal under every policy but the default. The policy is
+// Output rows: non-temporal under POL_NT_OUT. The policy is
 // a template parameter, not a runtime flag: the compiler merges a branch
 // between a plain and a non-temporal store into one plain store.
 template <int VEC, int POL>
@@ -193,7 +181,7 @@ enum { EM_FULL = 0, EM_SCALAR = 1, EM_HEAD = 2 };
 //  COPY_U : u                     U_MUL_E: w * u (fused into the reducer)
 //  COPY_E : e
 // `eoff` is the edge-feature column of f0 (f0, 0 or f0 / D by EM).
-template <int VEC, int MSG, int EM, int POL = POL_DEFAULT, bool BUF = false>
+template <int VEC, int MSG, int EM, bool BUF = false>
 struct SlotLoad {
   typedef typename Vec<VEC>::T V;
   V u;
@@ -204,7 +192,7 @@ struct SlotLoad {
                                        int32_t src, int64_t edge) {
     // ldu: row stride of ufeat in elements (F, or a padded width)
     if (MSG == DGLHIP_MSG_COPY_U_BF16) u = gather_bf16<VEC>(ufeat, src, ldu, f0);
-    else if (MSG != DGLHIP_MSG_COPY_E) u = gather_row<VEC, POL, BUF>(ufeat, src, ldu, f0);
+    else if (MSG != DGLHIP_MSG_COPY_E) u = gather_row<VEC, BUF>(ufeat, src, ldu, f0);
     if (!copies_u(MSG)) {
       if (EM == EM_FULL) e = ldv<VEC>(efeat + edge * F + f0);
       else e = Vec<VEC>::splat(efeat[edge * elen + eoff]);
@@ -214,8 +202,7 @@ struct SlotLoad {
 
 // Sequential reduction of slots [beg, end) of one row for the VEC features at
 // f0: the fma chain the reference's product runs (see the file header).
-template <int VEC, int UNROLL, int MSG, int EM, bool USE_EID, int POL = POL_DEFAULT,
-          bool BUF = false>
+template <int VEC, int UNROLL, int MSG, int EM, bool USE_EID, bool BUF = false>
 __device__ __forceinline__ typename Vec<VEC>::T reduce_range(
     typename Vec<VEC>::T acc, int64_t beg, int64_t end, int64_t ldu, int64_t F, int64_t f0,
     int64_t elen, int64_t eoff, const int32_t* __restrict__ indices,
@@ -223,7 +210,7 @@ __device__ __forceinline__ typename Vec<VEC>::T reduce_range(
     const float* __restrict__ efeat) {
   int64_t k = beg;
   for (; k + UNROLL <= end; k += UNROLL) {
-    SlotLoad<VEC, MSG, EM, POL, BUF> s[UNROLL];
+    SlotLoad<VEC, MSG, EM, BUF> s[UNROLL];
 #pragma unroll
     for (int j = 0; j < UNROLL; ++j)
       s[j].load(ufeat, efeat, ldu, F, f0, elen, eoff, indices[k + j],
@@ -240,7 +227,7 @@ __device__ __forceinline__ typename Vec<VEC>::T reduce_range(
   // load latencies per row, which dominates rows shorter than UNROLL)
   const int64_t rem = end - k;
   if (rem > 0) {
-    SlotLoad<VEC, MSG, EM, POL, BUF> s[UNROLL];
+    SlotLoad<VEC, MSG, EM, BUF> s[UNROLL];
 #pragma unroll
     for (int j = 0; j < UNROLL - 1; ++j)
       if (j < rem)
@@ -258,74 +245,27 @@ __device__ __forceinline__ typename Vec<VEC>::T reduce_range(
   return acc;
 }
 
-// Software-pipelined variant of reduce_range (copy_u only): the gathers of
-// batch t+1 are issued before batch t is accumulated, so 2 x UNROLL row
-// reads stay in flight across iterations instead of draining every batch.
-// Same per-element operation order (bit-identical results).
-template <int VEC, int UNROLL>
-__device__ __forceinline__ typename Vec<VEC>::T reduce_range_pipelined(
-    typename Vec<VEC>::T acc, int64_t beg, int64_t end, int64_t ldu, int64_t f0,
-    const int32_t* __restrict__ indices, const float* __restrict__ ufeat) {
-  typedef typename Vec<VEC>::T V;
-  int64_t k = beg;
-  if (k + UNROLL <= end) {
-    V cur[UNROLL];
-#pragma unroll
-    for (int j = 0; j < UNROLL; ++j) cur[j] = ldv<VEC>(ufeat + int64_t(indices[k + j]) * ldu + f0);
-    k += UNROLL;
-    for (; k + UNROLL <= end; k += UNROLL) {
-      V nxt[UNROLL];
-#pragma unroll
-      for (int j = 0; j < UNROLL; ++j)
-        nxt[j] = ldv<VEC>(ufeat + int64_t(indices[k + j]) * ldu + f0);
-#pragma unroll
-      for (int j = 0; j < UNROLL; ++j) acc += cur[j];
-#pragma unroll
-      for (int j = 0; j < UNROLL; ++j) cur[j] = nxt[j];
-    }
-#pragma unroll
-    for (int j = 0; j < UNROLL; ++j) acc += cur[j];
-  }
-  for (; k < end; ++k) acc += ldv<VEC>(ufeat + int64_t(indices[k]) * ldu + f0);
-  return acc;
-}
-
 // Cache policy of the running output row of accumulating items (the
 // blocked schedule's launches after the first read and rewrite each item's
 // row: 30 % of the fabric bytes, streaming through the L2s that hold the
-// gathered source block). RP (dglhip_set_row_policy, a study knob):
+// gathered source block). RP:
 //   0  plain load and store;
-//   1  non-temporal load and store;
 //   2  non-temporal load, store with sc1 (the line leaves the XCD's L2): the
-//      default (Reddit-shaped headline 3.83 -> 3.74 ms; policy 1 4.10; the
+//      accumulating launches (Reddit-shaped headline 3.83 -> 3.74 ms; the
 //      source rows keep the L2s);
-//   3  load with sc0 sc1 and store with sc1 (system scope both ways);
-//   4  plain load, store with sc1.
-// With 2-4 the first launch (which only writes its rows) stores with sc1 too.
-// Same values in every variant.
+//   4  plain load, store with sc1: the first launch, which only writes its rows.
+// Same values in every variant. (Non-temporal stores, 1, and system-scope
+// loads, 3, lost the r04 A/B and were removed: DESIGN.md §4.1.)
 template <int VEC, int RP>
 __device__ __forceinline__ typename Vec<VEC>::T load_out(const float* row, int64_t f0) {
   typedef typename Vec<VEC>::T V;
-  if (RP == 1 || RP == 2) return __builtin_nontemporal_load(reinterpret_cast<const V*>(row + f0));
-  if (RP == 3 && VEC == 2) {
-    typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-    const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(row), 0, 0x7fffffff, 0x00020000);
-    const u32x2 w = __builtin_amdgcn_raw_buffer_load_b64(
-        r, static_cast<uint32_t>(f0 * int64_t(sizeof(float))), 0, 1 | 16);
-    return *reinterpret_cast<const V*>(&w);
-  }
+  if (RP == 2) return __builtin_nontemporal_load(reinterpret_cast<const V*>(row + f0));
   return ldv<VEC>(row + f0);
 }
 
 template <int VEC, int RP>
 __device__ __forceinline__ void store_out(float* row, int64_t f0, typename Vec<VEC>::T v) {
-  typedef typename Vec<VEC>::T V;
-  if (RP == 1) {
-    __builtin_nontemporal_store(v, reinterpret_cast<V*>(row + f0));
-    return;
-  }
-  if ((RP == 2 || RP == 3 || RP == 4) && VEC == 2) {
+  if ((RP == 2 || RP == 4) && VEC == 2) {
     typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
     const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(row, 0, 0x7fffffff,
                                                                        0x00020000);
@@ -334,7 +274,7 @@ __device__ __forceinline__ void store_out(float* row, int64_t f0, typename Vec<V
                                           0, 16);
     return;
   }
-  if ((RP == 2 || RP == 3 || RP == 4) && VEC == 4) {
+  if ((RP == 2 || RP == 4) && VEC == 4) {
     typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
     const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(row, 0, 0x7fffffff,
                                                                        0x00020000);
@@ -354,7 +294,7 @@ __device__ __forceinline__ void store_out(float* row, int64_t f0, typename Vec<V
 // MEAN and ACCUM on whole rows the row's mean is added to the value in
 // out[i, :] (out + mean: a sum of two terms, the same bits either way round).
 template <int VEC, int GROUP, int UNROLL, int MSG, int EM, bool MEAN, bool CHUNKED,
-          bool ACCUM, bool PIPE = false, int POL = POL_DEFAULT, bool BUF = false, int RP = 0>
+          bool ACCUM, int POL = POL_DEFAULT, bool BUF = false, int RP = 0>
 __global__ __launch_bounds__(256) void gspmm_sum_kernel(
     int64_t num_items, int64_t F, int64_t elen, int64_t ldu,
     const int64_t* __restrict__ indptr,
@@ -391,10 +331,8 @@ __global__ __launch_bounds__(256) void gspmm_sum_kernel(
     const int64_t eoff = EM == EM_HEAD ? f0 / (F / elen) : (EM == EM_FULL ? f0 : 0);
     constexpr bool ADD_MEAN = MEAN && ACCUM && !CHUNKED;
     V acc = (ACCUM && !ADD_MEAN) ? load_out<VEC, RP>(out + row * F, f0) : Vec<VEC>::zero();
-    if (PIPE && MSG == DGLHIP_MSG_COPY_U)
-      acc = reduce_range_pipelined<VEC, UNROLL>(acc, beg, end, ldu, f0, indices, ufeat);
-    else if (copies_u(MSG) || eid != nullptr)  // uniform branch
-      acc = reduce_range<VEC, UNROLL, MSG, EM, true, POL, BUF && GROUP == 64>(
+    if (copies_u(MSG) || eid != nullptr)  // uniform branch
+      acc = reduce_range<VEC, UNROLL, MSG, EM, true, BUF && GROUP == 64>(
           acc, beg, end, ldu, F, f0, elen, eoff, indices, eid, ufeat, efeat);
     else
       acc = reduce_range<VEC, UNROLL, MSG, EM, false>(acc, beg, end, ldu, F, f0, elen, eoff, indices,
@@ -560,9 +498,9 @@ static inline int pick_vec(int64_t F, std::initializer_list<const void*> ptrs) {
       if (p && (reinterpret_cast<uintptr_t>(p) % bytes) != 0) return false;
     return true;
   };
-  // no VEC 4 by default: at F=256 one 1-KB row per wave instruction (8 gathers
+  // no VEC 4: at F=256 one 1-KB row per wave instruction (8 gathers
   // in flight) ran 16.3 ms against 15.7 ms for two VEC-2 passes with 16 in
-  // flight (tools/feat_sweep.py, Reddit-shaped graph)
+  // flight (profiles/r01/feat_sweep_reddit.json, Reddit-shaped graph)
   if (F % 2 == 0 && F >= 4 && aligned(8)) return 2;
   return 1;
 }
@@ -577,7 +515,7 @@ static inline int pick_group(int64_t F, int vec) {
 // Rows of 16..64 floats take a whole wave each (idle lanes) rather than
 // sharing one: the slot stream is then wave-uniform (column ids through the
 // scalar cache) instead of a per-lane index load ahead of every gather.
-// tools/feat_sweep.py, Reddit-shaped graph: F=16 2.18 -> 1.73 ms, F=32
+// profiles/r01/feat_sweep_reddit.json, Reddit-shaped graph: F=16 2.18 -> 1.73 ms, F=32
 // 2.12 -> 1.74 ms, F=64 level.
 static inline void one_row_per_wave(int64_t F, int& vec, int& group) {
   if (group < 64 && F >= 16) {
@@ -604,146 +542,66 @@ struct SumLaunch {
 
 // Outputs past twice the 256 MiB Infinity Cache are stored non-temporally
 // (POL_NT_OUT): streamed out, they would evict the feature rows that are
-// gathered again (RMAT-26, 34 GB out: 94.1 -> 89.5 ms,
-// tools/cache_policy_study.py). Covers copy_u + sum at VEC 2 x 64 lanes.
+// gathered again (RMAT-26, 34 GB out: 94.1 -> 89.5 ms, DESIGN.md, the r01
+// cache-policy study). Covers copy_u + sum at VEC 2 x 64 lanes.
 static inline bool stream_output(int64_t rows, int64_t feat_len) {
   return rows * feat_len * int64_t(sizeof(float)) > (int64_t(512) << 20);
 }
 
-// Tuning override for the copy_u + sum shape (dglhip_set_spmm_variant);
-// 0 = automatic choice.
-extern int g_var_vec, g_var_group, g_var_unroll, g_var_pipe;
-// Cache policy for copy_u + sum at VEC 2 x 64 lanes (dglhip_set_cache_policy).
-// -1: automatic (non-temporal output past 512 MiB, default otherwise).
-extern int g_cache_policy;
-// Row gathers of copy_u + sum at VEC 2 x 64 lanes through buffer descriptors
-// (dglhip_set_gather_mode), a bit mask: bit 0 the one-launch rows and the
-// heavy-row chunk launches, bit 1 the blocked schedule's item launches, the
-// first block's included (the default, 2); 0 global loads everywhere.
-extern int g_gather_buf;
-// Running-row cache policy of the blocked schedule's copy_u + sum item
-// launches (load_out / store_out; dglhip_set_row_policy): 2 by default. It
-// applies where no output cache policy does (g_cache_policy automatic with
-// an output under twice the Infinity Cache, or 0): an explicit or automatic
-// non-temporal output (POL_NT_OUT and the study policies) takes precedence.
-extern int g_row_pol;
-
-template <int VEC, int GROUP, int MSG, int EM, bool MEAN, int UNROLL_OVERRIDE = 0,
-          bool PIPE = false>
+template <int VEC, int GROUP, int MSG, int EM, bool MEAN>
 static inline void launch_sum(const SumLaunch& a, hipStream_t stream) {
   // 16 row gathers in flight per lane group: measured +22% over 8 on HBM-bound
-  // RMAT (tools/kernel_sweep.py), neutral on the MALL-resident Reddit table
-  constexpr int UNROLL = UNROLL_OVERRIDE ? UNROLL_OVERRIDE : ((VEC == 4) ? 8 : 16);
+  // RMAT, neutral on the MALL-resident Reddit table
+  constexpr int UNROLL = 16;
   constexpr int ITEMS_PER_BLOCK = 4 * (64 / GROUP);
   const int64_t blocks = (a.num_items + ITEMS_PER_BLOCK - 1) / ITEMS_PER_BLOCK;
   DGLHIP_CHECK(blocks <= 0x7fffffff, "grid too large: " << blocks);
   if (blocks == 0) return;
-  constexpr bool POL_OK = MSG == DGLHIP_MSG_COPY_U && VEC == 2 && GROUP == 64 && !MEAN &&
-                         !PIPE && UNROLL_OVERRIDE == 0;
-  const int pol = !POL_OK ? POL_DEFAULT
-                  : g_cache_policy >= 0 ? g_cache_policy
-                  : a.nt_out ? POL_NT_OUT : POL_DEFAULT;
-  timed_launch(stream, [&] {
-    // the running-row cache policy study (dglhip_set_row_policy): only the
-    // shapes POL_OK covers are instantiated
-    if constexpr (POL_OK) {
-      // the blocked schedule's items only (item rows given; heavy-row chunk
-      // and row-range launches keep their own policy: r04 ADVICE)
-      if (a.chunk_beg && a.row_order && pol == POL_DEFAULT && g_row_pol > 0 &&
-          (a.accumulate || g_row_pol >= 2)) {
-#define DGLHIP_RP_LAUNCH_B(ACC, RPV, B)                                                         \
-  hipLaunchKernelGGL((gspmm_sum_kernel<VEC, GROUP, UNROLL, MSG, EM, MEAN, true, ACC, false,     \
-                                       POL_DEFAULT, B, RPV>),                                   \
-                     grid_1d(blocks), dim3(256), 0, stream, a.num_items, a.F, a.elen,           \
-                     a.ldu ? a.ldu : a.F, a.indptr, a.indices, a.eid, a.ufeat, a.efeat, a.out,  \
-                     a.row_order, a.chunk_beg, a.chunk_end)
-#define DGLHIP_RP_LAUNCH(ACC, RPV) DGLHIP_RP_LAUNCH_B(ACC, RPV, false)
-        if ((g_gather_buf & 2) && g_row_pol == 2) {
-          // the default: row gathers through per-row buffer descriptors (the
-          // row base in SGPRs, one lane offset for all 16: 42 instead of 70
-          // VGPRs, 8 waves per SIMD instead of 7; Reddit-shaped headline
-          // 3.74 -> 3.61 ms, same bits, tools/gather_mode_ab.py)
-          if (!a.accumulate) DGLHIP_RP_LAUNCH_B(false, 4, true);
-          else DGLHIP_RP_LAUNCH_B(true, 2, true);
-          return;
-        }
-        if (!a.accumulate) DGLHIP_RP_LAUNCH(false, 4);  // the first launch: stores only
-        else if (g_row_pol == 1) DGLHIP_RP_LAUNCH(true, 1);
-        else if (g_row_pol == 2) DGLHIP_RP_LAUNCH(true, 2);
-        else if (g_row_pol == 3) DGLHIP_RP_LAUNCH(true, 3);
-        else DGLHIP_RP_LAUNCH(true, 4);
-#undef DGLHIP_RP_LAUNCH
-#undef DGLHIP_RP_LAUNCH_B
-        return;
-      }
+  const bool chunked = a.chunk_beg != nullptr;
+  // every instantiation has one signature: choose the kernel, then launch it
+  auto kernel = gspmm_sum_kernel<VEC, GROUP, UNROLL, MSG, EM, MEAN, false, false>;
+  if (chunked && a.accumulate)
+    kernel = gspmm_sum_kernel<VEC, GROUP, UNROLL, MSG, EM, MEAN, true, true>;
+  else if (chunked)
+    kernel = gspmm_sum_kernel<VEC, GROUP, UNROLL, MSG, EM, MEAN, true, false>;
+  else if (a.accumulate)
+    kernel = gspmm_sum_kernel<VEC, GROUP, UNROLL, MSG, EM, MEAN, false, true>;
+  // copy_u + sum with a whole wave of two-float lanes per row (F = 128 and
+  // wider): the one shape with an output policy, buffer-descriptor gathers
+  // and a running-row policy
+  constexpr bool POL_OK = MSG == DGLHIP_MSG_COPY_U && VEC == 2 && GROUP == 64 && !MEAN;
+  if constexpr (POL_OK) {
+    if (chunked && a.row_order && !a.nt_out) {
+      // the blocked schedule's items (item rows given; heavy-row chunk and
+      // row-range launches keep the generic kernels: r04 ADVICE). Row gathers
+      // through per-row buffer descriptors (the row base in SGPRs, one lane
+      // offset for all 16: 42 instead of 70 VGPRs, 8 waves per SIMD instead of
+      // 7; Reddit-shaped headline 3.74 -> 3.61 ms, same bits); the running
+      // rows under RP 2, the first launch, which only stores, under RP 4.
+      if (a.accumulate)
+        kernel = gspmm_sum_kernel<VEC, GROUP, UNROLL, MSG, EM, false, true, true, POL_DEFAULT,
+                                  true, 2>;
+      else
+        kernel = gspmm_sum_kernel<VEC, GROUP, UNROLL, MSG, EM, false, true, false, POL_DEFAULT,
+                                  true, 4>;
+    } else if (a.nt_out && !a.accumulate) {
+      // an output past twice the Infinity Cache (stream_output)
+      if (chunked)
+        kernel = gspmm_sum_kernel<VEC, GROUP, UNROLL, MSG, EM, false, true, false, POL_NT_OUT>;
+      else
+        kernel = gspmm_sum_kernel<VEC, GROUP, UNROLL, MSG, EM, false, false, false, POL_NT_OUT>;
     }
-#define DGLHIP_POL_LAUNCH_B(CH, P, B)                                                      \
-  hipLaunchKernelGGL((gspmm_sum_kernel<VEC, GROUP, UNROLL, MSG, EM, false, CH, false, false, P, B>), \
-                     grid_1d(blocks), dim3(256), 0, stream, a.num_items,   \
-                     a.F, a.elen, a.ldu ? a.ldu : a.F, a.indptr, a.indices, a.eid, a.ufeat, a.efeat, a.out,         \
-                     a.row_order, a.chunk_beg, a.chunk_end)
-#define DGLHIP_POL_LAUNCH(CH, P) DGLHIP_POL_LAUNCH_B(CH, P, false)
-    if (POL_OK && (g_gather_buf & 1) && !a.accumulate && (pol == POL_DEFAULT || pol == POL_NT_OUT)) {
-      // row gathers through buffer descriptors (gather_row_buf)
-      const bool ch = a.chunk_beg != nullptr;
-      if (pol == POL_DEFAULT) { if (ch) DGLHIP_POL_LAUNCH_B(true, POL_DEFAULT, true); else DGLHIP_POL_LAUNCH_B(false, POL_DEFAULT, true); }
-      else { if (ch) DGLHIP_POL_LAUNCH_B(true, POL_NT_OUT, true); else DGLHIP_POL_LAUNCH_B(false, POL_NT_OUT, true); }
-    } else if (POL_OK && pol != POL_DEFAULT && !a.accumulate) {
-      const bool ch = a.chunk_beg != nullptr;
-      if (pol == POL_NT) { if (ch) DGLHIP_POL_LAUNCH(true, POL_NT); else DGLHIP_POL_LAUNCH(false, POL_NT); }
-      else if (pol == POL_HOT) { if (ch) DGLHIP_POL_LAUNCH(true, POL_HOT); else DGLHIP_POL_LAUNCH(false, POL_HOT); }
-      else { if (ch) DGLHIP_POL_LAUNCH(true, POL_NT_OUT); else DGLHIP_POL_LAUNCH(false, POL_NT_OUT); }
-    } else if (a.chunk_beg && a.accumulate)
-      hipLaunchKernelGGL((gspmm_sum_kernel<VEC, GROUP, UNROLL, MSG, EM, MEAN, true, true>),
-                         grid_1d(blocks), dim3(256), 0, stream,
-                         a.num_items, a.F, a.elen, a.ldu ? a.ldu : a.F, a.indptr, a.indices, a.eid, a.ufeat, a.efeat,
-                         a.out, a.row_order, a.chunk_beg, a.chunk_end);
-    else if (!a.chunk_beg && a.accumulate)
-      hipLaunchKernelGGL((gspmm_sum_kernel<VEC, GROUP, UNROLL, MSG, EM, MEAN, false, true>),
-                         grid_1d(blocks), dim3(256), 0, stream,
-                         a.num_items, a.F, a.elen, a.ldu ? a.ldu : a.F, a.indptr, a.indices, a.eid, a.ufeat, a.efeat,
-                         a.out, a.row_order, a.chunk_beg, a.chunk_end);
-    else if (a.chunk_beg)
-      hipLaunchKernelGGL((gspmm_sum_kernel<VEC, GROUP, UNROLL, MSG, EM, MEAN, true, false>),
-                         grid_1d(blocks), dim3(256), 0, stream,
-                         a.num_items, a.F, a.elen, a.ldu ? a.ldu : a.F, a.indptr, a.indices, a.eid, a.ufeat, a.efeat,
-                         a.out, a.row_order, a.chunk_beg, a.chunk_end);
-    else
-      hipLaunchKernelGGL((gspmm_sum_kernel<VEC, GROUP, UNROLL, MSG, EM, MEAN, false, false, PIPE>),
-                         grid_1d(blocks), dim3(256), 0, stream,
-                         a.num_items, a.F, a.elen, a.ldu ? a.ldu : a.F, a.indptr, a.indices, a.eid, a.ufeat, a.efeat,
-                         a.out, a.row_order, a.chunk_beg, a.chunk_end);
-#undef DGLHIP_POL_LAUNCH
-#undef DGLHIP_POL_LAUNCH_B
-  });
-}
-
-template <int MSG, int EM, bool MEAN>
-static inline bool dispatch_variant(const SumLaunch& a, hipStream_t stream) {
-  if (MSG != DGLHIP_MSG_COPY_U || MEAN || g_var_vec == 0 || a.accumulate) return false;
-  const int v = g_var_vec, gr = g_var_group, u = g_var_unroll, pp = g_var_pipe;
-  if (int64_t(v) * gr < a.F && (a.F % (int64_t(v) * gr)) != 0) return false;
-  if (a.F % v != 0) return false;
-#define DGLHIP_VAR(V, G, U, P)                                                   \
-  if (v == V && gr == G && u == U && pp == P) {                                \
-    launch_sum<V, G, MSG, EM, MEAN, U, P>(a, stream);                          \
-    return true;                                                               \
   }
-  DGLHIP_VAR(2, 64, 4, 0) DGLHIP_VAR(2, 64, 8, 0) DGLHIP_VAR(2, 64, 16, 0)
-  DGLHIP_VAR(2, 64, 32, 0) DGLHIP_VAR(4, 32, 8, 0) DGLHIP_VAR(4, 32, 16, 0)
-  DGLHIP_VAR(4, 32, 32, 0) DGLHIP_VAR(2, 64, 8, 1) DGLHIP_VAR(2, 64, 16, 1)
-  DGLHIP_VAR(4, 32, 8, 1) DGLHIP_VAR(4, 32, 16, 1)
-  // narrow rows (F < 128, or F not a multiple of 2 x 64): tools/feat_sweep.py
-  DGLHIP_VAR(1, 64, 8, 0) DGLHIP_VAR(1, 64, 16, 0) DGLHIP_VAR(1, 64, 32, 0)
-  DGLHIP_VAR(2, 32, 16, 0) DGLHIP_VAR(2, 32, 32, 0) DGLHIP_VAR(1, 32, 32, 0)
-#undef DGLHIP_VAR
-  return false;
+  timed_launch(stream, [&] {
+    hipLaunchKernelGGL(kernel, grid_1d(blocks), dim3(256), 0, stream, a.num_items, a.F, a.elen,
+                       a.ldu ? a.ldu : a.F, a.indptr, a.indices, a.eid, a.ufeat, a.efeat, a.out,
+                       a.row_order, a.chunk_beg, a.chunk_end);
+  });
 }
 
 template <int MSG, int EM, bool MEAN>
 static inline void dispatch_sum_shape(const SumLaunch& a, hipStream_t stream) {
   const int64_t F = a.F;
-  if (dispatch_variant<MSG, EM, MEAN>(a, stream)) return;
   int vec = pick_vec(F, {a.ufeat, EM == EM_FULL ? a.efeat : nullptr, a.out});
   // per-head weights: a lane's VEC features must stay inside one head
   while (EM == EM_HEAD && vec > 1 && (F / a.elen) % vec != 0) vec >>= 1;
@@ -816,18 +674,18 @@ static inline void dispatch_max_shape(const MaxLaunch& a, hipStream_t stream) {
 // One (message, edge layout) pair of the sum/mean and max reducers. Defined
 // only in gspmm_inst.hip, which explicitly instantiates it per pair.
 template <int MSG, int EM>
-void dispatch_sum_me(bool mean, const SumLaunch& a, hipStream_t stream);
+void dispatch_me(bool mean, const SumLaunch& a, hipStream_t stream);
 template <int MSG, int EM>
-void dispatch_max_me(const MaxLaunch& a, hipStream_t stream);
+void dispatch_me(const MaxLaunch& a, hipStream_t stream);
 
 #ifdef GSPMM_INST_MSG
 template <int MSG, int EM>
-void dispatch_sum_me(bool mean, const SumLaunch& a, hipStream_t stream) {
+void dispatch_me(bool mean, const SumLaunch& a, hipStream_t stream) {
   if (mean) dispatch_sum_shape<MSG, EM, true>(a, stream);
   else dispatch_sum_shape<MSG, EM, false>(a, stream);
 }
 template <int MSG, int EM>
-void dispatch_max_me(const MaxLaunch& a, hipStream_t stream) {
+void dispatch_me(const MaxLaunch& a, hipStream_t stream) {
   dispatch_max_shape<MSG, EM>(a, stream);
 }
 #endif

@@ -5,9 +5,8 @@
 #include "gspmm_impl.h"
 
 namespace dglhip {
-template void dispatch_sum_me<GSPMM_INST_MSG, GSPMM_INST_EM>(bool, const SumLaunch&,
-                                                             hipStream_t);
-template void dispatch_max_me<GSPMM_INST_MSG, GSPMM_INST_EM>(const MaxLaunch&, hipStream_t);
+template void dispatch_me<GSPMM_INST_MSG, GSPMM_INST_EM>(bool, const SumLaunch&, hipStream_t);
+template void dispatch_me<GSPMM_INST_MSG, GSPMM_INST_EM>(const MaxLaunch&, hipStream_t);
 }  // namespace dglhip
 
 #if GSPMM_INST_MSG == 0 && GSPMM_INST_EM == 1  // copy_u, scalar layout: the headline kernel

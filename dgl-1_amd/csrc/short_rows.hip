@@ -68,7 +68,7 @@ __global__ __launch_bounds__(256) void gspmm_short_rows_kernel(
             if (b + j < deg[r]) {
               const int32_t c = slot_cols[beg[r] + b + j];
               if (MSG == DGLHIP_MSG_COPY_U_BF16) v[r][j] = gather_bf16<VEC>(ufeat, c, ldu, f0);
-              else v[r][j] = gather_row<VEC, POL_DEFAULT>(ufeat, c, ldu, f0);
+              else v[r][j] = gather_row<VEC, false>(ufeat, c, ldu, f0);
             }
 #pragma unroll
         for (int r = 0; r < R; ++r)

@@ -160,8 +160,6 @@ def _load():
         "dglhip_set_sweep_per_cu": (_c_int, [_c_int]),
         "dglhip_sweep_barrier_expiries": (_c_int, [_c_int, _vp]),
         "dglhip_set_sweep_rows": (_c_int, [_c_int]),
-        "dglhip_set_pair_slots": (_c_int, [_c_int]),
-        "dglhip_gspmm_pair_items_ok": (_c_int, [_c_int, _c_i64, _c_i64, _c_i64]),
         "dglhip_get_sweep_rows": (_c_int, [_vp]),
         "dglhip_set_sweep_schedule": (_c_int, [_c_int, _c_i64, _c_i64, _c_int, _c_int, _c_i64,
                                                _c_i64, _c_int]),
@@ -197,10 +195,6 @@ def _load():
                                         _vp, _c_int]),
         "dglhip_timing_enable": (_c_int, [_c_int]),
         "dglhip_gspmm_resident_waves": (_c_int, [_c_int, ctypes.POINTER(_c_i64)]),
-        "dglhip_set_spmm_variant": (_c_int, [_c_int, _c_int, _c_int, _c_int]),
-        "dglhip_set_cache_policy": (_c_int, [_c_int]),
-        "dglhip_set_row_policy": (_c_int, [_c_int]),
-        "dglhip_set_gather_mode": (_c_int, [_c_int]),
         "dglhip_set_sddmm_variant": (_c_int, [_c_int]),
         "dglhip_gspmm_short_rows_device": (_c_int, [_c_int, _c_int, _c_i64, _c_i64, _c_i64,
                                                     _c_i64, _vp, _vp, _vp, _vp, _vp, _c_i64, _vp]),

@@ -1407,16 +1407,6 @@ def gspmm_ranges(msg, beg, end, accumulate, indices, out, ufeat=None, efeat=None
     return out
 
 
-def set_gather_mode(mode):
-    """Study knob: where the copy_u + sum kernel's row gathers go through
-    buffer descriptors instead of global loads, a bit mask (bit 0 one-launch
-    calls, bit 1 the blocked schedule's launches: the default, 2); True = 3,
-    False = 0. Same values."""
-    if isinstance(mode, bool):
-        mode = 3 if mode else 0
-    check_call(LIB.dglhip_set_gather_mode(int(mode)))
-
-
 def set_sddmm_variant(alternate):
     """Study knob for the sliced g-SDDMM dot: bit 0 runs it at its
     alternative depth of slots in flight, bit 1 loads the GAT epilogue's

@@ -472,15 +472,6 @@ int dglhip_gspmm_host(int msg_op, int reduce_op, int64_t num_rows,
                       int64_t efeat_len, float* out, int64_t* arg_out,
                       int num_threads);
 
-/* Knob: where the copy_u + sum kernel's row gathers (two floats per lane, a
- * wave per row) go through buffer descriptors built from the wave-uniform row
- * address (one 32-bit lane offset for every gather in flight instead of a
- * 64-bit address each) rather than global loads, as a bit mask: bit 0 the
- * one-launch rows and heavy-row chunk launches, bit 1 the source-blocked
- * schedule's item launches, the first block's included (the default, 2: 42
- * instead of 70 VGPRs there). Same values. */
-int dglhip_set_gather_mode(int buffer_descriptors);
-
 /* Resident waves of the headline g-SpMM kernel (F = 128 copy_u + sum) on
  * `device`: compute units x the kernel's occupancy per CU (blocks of 4 waves).
  * The heavy-row policy sizes its critical-path test and its chunk launches
@@ -585,27 +576,6 @@ int dglhip_gspmm_items_device(int msg_op, int64_t num_items, int64_t feat_len,
                               const int32_t* indices, const int64_t* eid, const float* ufeat,
                               int64_t ufeat_ld, const float* efeat, int64_t efeat_len,
                               float* out, void* stream);
-
-/* Narrow rows, two slots per gather (r06): the same items as
- * dglhip_gspmm_items_device (copy_u + sum, item i = row item_rows[i] over
- * slots [item_ptr[i], item_ptr[i + 1]), accumulate continuing the chains)
- * for source rows of 16..64 floats at an even stride ufeat_ld <= 64 (0 =
- * feat_len) over a table of num_src_rows rows under 2 GiB. The wave's halves
- * gather consecutive slots and the lower half adds them in slot order, so the
- * results equal dglhip_gspmm_items_device's bit for bit with half the gather
- * instructions. _ok: 1 when a shape qualifies (and the knob is on). */
-int dglhip_gspmm_pair_items_ok(int msg_op, int64_t feat_len, int64_t ufeat_ld,
-                               int64_t num_src_rows);
-int dglhip_gspmm_pair_items_device(int64_t num_items, int64_t feat_len, int64_t ufeat_ld,
-                                   int64_t num_src_rows, const int32_t* item_rows,
-                                   const int64_t* item_ptr, int accumulate,
-                                   const int32_t* indices, const float* ufeat, float* out,
-                                   void* stream);
-/* Study knob: the plan's blocked copy_u + sum takes the paired kernel where
- * it qualifies (1), or never (0, the default: measured slower, 4.15 vs 2.14
- * ms at F = 41 on the Reddit-shaped graph); env
- * DGLHIP_PAIR_SLOTS. */
-int dglhip_set_pair_slots(int on);
 
 /* Source-swept copy_u + sum (mean != 0: mean) of fp32 rows of feat_len = 64,
  * 128 or 256 floats over the CSR (indptr, indices), every row of out
@@ -1095,28 +1065,6 @@ int dglhip_distmult_grad_host(int task, int64_t num_rows, int64_t feat_len, int6
 /* g-SpMM launch is bracketed by a pair of hipEvents on its own stream.     */
 /* ------------------------------------------------------------------------ */
 int dglhip_timing_enable(int enable);
-/* Tuning knob for copy_u + sum: force (vec floats/lane, lanes/row, gathers
- * per batch, software-pipelined batches) for subsequent launches; vec = 0
- * restores the automatic choice. Results are identical for every variant
- * (same per-element chain). */
-int dglhip_set_spmm_variant(int vec, int group, int unroll, int pipelined);
-/* Cache policy of copy_u + sum's source-row gathers and output stores (VEC 2 x
- * 64-lane shape; results are identical under every policy):
- *  -1 automatic (the default): non-temporal output stores when the output
- *     exceeds 512 MiB (twice the Infinity Cache), default policy otherwise;
- *   0 default policy; 1 all non-temporal; 2 "hot" rows (column id with bit 31
- *   set by the caller, on a CSR copy no other kernel reads) default and the
- *   rest non-temporal; 3 non-temporal output stores only. */
-int dglhip_set_cache_policy(int policy);
-/* Study knob: the cache policy of the running output rows that accumulating
- * copy_u + sum items (the source-blocked schedule's later launches) read and
- * rewrite (and the fused GAT layer's 8-head rows): 0 plain, 1 non-temporal
- * load and store, 2 non-temporal load + sc1 store (the default), 3 sc0 sc1
- * load + sc1 store, 4 plain load + sc1 store (2-4: the first launch's stores
- * with sc1 too). Item launches only, and only where no output cache policy
- * (dglhip_set_cache_policy, or the automatic non-temporal output past twice
- * the Infinity Cache) applies. Same values. */
-int dglhip_set_row_policy(int policy);
 /* Synchronises on the recorded events and returns the summed kernel time
  * (ms) and launch count since the last enable/reset. */
 int dglhip_timing_read(double* total_ms, int64_t* launches);

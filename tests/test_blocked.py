@@ -145,19 +145,15 @@ def test_blocked_device_bits(F, reduce):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("F,level", [(16, 1), (32, 1), (41, 1), (48, 1), (64, 1)])
-def test_paired_narrow_rows_same_bits(F, level):
-    """Narrow source rows (<= 64 floats at an even stride: F = 41 runs at its
-    48-float padded stride) take the paired kernel on the blocked schedule
-    (dglhip_gspmm_pair_items_device: the wave's halves gather consecutive
-    slots, the lower half adds them in slot order). Forward, the transposed
-    backward, mean and a continued (SUM_ACCUM) product equal the one-row-
-    per-wave kernel bit for bit, and the oracle's chains; rows of 1, 2 and 3
-    slots and odd tails included. (A study kernel, off by default: it
-    measured slower)"""
+@pytest.mark.parametrize("F", [16, 32, 41, 48, 64])
+def test_blocked_narrow_rows_same_bits(F):
+    """Narrow source rows (<= 64 floats: F = 41 runs at its 48-float padded
+    stride) on the blocked schedule: forward, the transposed backward, mean
+    and a continued (SUM_ACCUM) product equal the one-launch run bit for bit,
+    and the oracle's chains; rows of 1, 2 and 3 slots and odd tails
+    included."""
     if not torch.cuda.is_available():
         pytest.skip("no ROCm device")
-    from dgl._ffi import LIB, check_call
     dev = torch.device("cuda", 0)
     n, m = 120_000, 8_000_000
     src, dst = _graph(n, m, 5, True)
@@ -172,15 +168,9 @@ def test_paired_narrow_rows_same_bits(F, level):
     G = torch.randn(n, F, generator=gen)
     base = torch.randn(n, F, generator=gen)
     adj = g.sparse_adjacency(dev)
-    ld = kernel.padded_width(F)
-    check_call(LIB.dglhip_set_pair_slots(level))
-    try:
-        assert LIB.dglhip_gspmm_pair_items_ok(0, F, ld, n) == 1
-    finally:
-        check_call(LIB.dglhip_set_pair_slots(0))
 
-    def run(pair):
-        check_call(LIB.dglhip_set_pair_slots(pair))
+    def run(policy):
+        old = kernel.set_blocked(policy)
         try:
             h = H.to(dev).requires_grad_(True)
             g.ndata["h"] = h
@@ -192,15 +182,15 @@ def test_paired_narrow_rows_same_bits(F, level):
             torch.cuda.synchronize()
             return [g.ndata["o"].detach().cpu(), h.grad.cpu(), g.ndata["mo"].cpu(), acc.cpu()]
         finally:
-            check_call(LIB.dglhip_set_pair_slots(0))
+            kernel.set_blocked(old)
     # small tables: blocks of 2 MiB so that every width takes the blocked schedule
     with kernel.scheduled(block_table_min=0, block_bytes=2 << 20, block_min_row_bytes=0):
         assert kernel._block_plan(adj.fwd, H.to(dev), F) is not None
-        paired, single = run(level), run(0)
-    for a, b in zip(paired, single):
+        blocked, single = run("auto"), run("off")
+    for a, b in zip(blocked, single):
         assert torch.equal(a, b)
-    assert np.array_equal(paired[0].numpy(), O.spmm_coo(n, dst, src, H.numpy()))
-    assert np.array_equal(paired[1].numpy(), O.spmm_coo(n, src, dst, G.numpy()))
+    assert np.array_equal(blocked[0].numpy(), O.spmm_coo(n, dst, src, H.numpy()))
+    assert np.array_equal(blocked[1].numpy(), O.spmm_coo(n, src, dst, G.numpy()))
 
 
 @pytest.mark.gpu
@@ -592,61 +582,6 @@ def test_one_csr_two_block_counts_device():
                 assert np.array_equal(out.numpy(), O.spmm_coo(n, dst, src, H.numpy()))
     finally:
         kernel.set_schedule_policy(**old)
-
-
-@pytest.mark.gpu
-def test_row_policies_same_bits():
-    """The running-row cache policies of the blocked launches
-    (dglhip_set_row_policy: non-temporal / sc1 loads and stores) change where
-    lines live, not values: every policy gives the default's bits."""
-    if not torch.cuda.is_available():
-        pytest.skip("no ROCm device")
-    dev = torch.device("cuda", 0)
-    n, m = 120_000, 8_000_000
-    src, dst = _graph(n, m, 19, True)
-    adj = kernel.from_coo(n, n, torch.from_numpy(dst), torch.from_numpy(src),
-                          kernel.ORDER_EID, dev)
-    H = torch.randn(n, 128, generator=torch.Generator().manual_seed(20)).to(dev)
-    assert kernel.blocked_schedule(adj, H) >= 2
-    ref = kernel.gspmm(adj, "copy_u", "sum", H)
-    try:
-        for pol in range(5):
-            kernel.check_call(kernel.LIB.dglhip_set_row_policy(pol))
-            assert torch.equal(kernel.gspmm(adj, "copy_u", "sum", H), ref)
-    finally:
-        kernel.check_call(kernel.LIB.dglhip_set_row_policy(2))  # the default
-
-
-@pytest.mark.gpu
-def test_gather_modes_same_bits():
-    """Row gathers through buffer descriptors (dglhip_set_gather_mode: bit 0
-    one-launch calls, bit 1 the blocked launches, the default 2) or global
-    loads load the same rows: every mode gives the default's bits, blocked and
-    in one launch, under the row policies the blocked launches pair them with."""
-    if not torch.cuda.is_available():
-        pytest.skip("no ROCm device")
-    dev = torch.device("cuda", 0)
-    n, m = 120_000, 8_000_000
-    src, dst = _graph(n, m, 23, True)
-    adj = kernel.from_coo(n, n, torch.from_numpy(dst), torch.from_numpy(src),
-                          kernel.ORDER_EID, dev)
-    H = torch.randn(n, 128, generator=torch.Generator().manual_seed(24)).to(dev)
-    assert kernel.blocked_schedule(adj, H) >= 2
-    refs = {}
-    try:
-        for blocked in ("auto", "off"):
-            kernel.set_blocked(blocked)
-            refs[blocked] = kernel.gspmm(adj, "copy_u", "sum", H)
-            for mode in range(4):
-                kernel.set_gather_mode(mode)
-                for pol in (2, 4):
-                    kernel.check_call(kernel.LIB.dglhip_set_row_policy(pol))
-                    assert torch.equal(kernel.gspmm(adj, "copy_u", "sum", H), refs[blocked])
-        assert torch.equal(refs["auto"], refs["off"])
-    finally:
-        kernel.set_blocked("auto")
-        kernel.set_gather_mode(2)
-        kernel.check_call(kernel.LIB.dglhip_set_row_policy(2))
 
 
 @pytest.mark.gpu
