@@ -620,3 +620,171 @@ int dglhip_gsddmm_host(int op, int64_t num_rows, int64_t feat_len, int64_t num_h
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------------------
+// Segment reduction on the host: the chains and the chunk order of
+// segment_reduce.hip (identical bits). Products and sums round separately.
+// ---------------------------------------------------------------------------
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
+
+namespace {
+
+inline void seg_max_step(float v, int64_t r, float& best, int64_t& arg) {
+  if (!(best != best) && (v > best || v != v)) {
+    best = v;
+    arg = r;
+  }
+}
+
+// one chunk: rows [r0, r1) into acc[F] (and the weight chain / the argmax)
+void seg_chunk(bool is_max, int64_t F, int64_t r0, int64_t r1, const float* x, int64_t ldx,
+               const float* w, float* acc, float* wacc, int64_t* best) {
+  if (is_max) {
+    for (int64_t f = 0; f < F; ++f) {
+      acc[f] = r0 < r1 ? x[r0 * ldx + f] : 0.0f;
+      best[f] = r0 < r1 ? r0 : -1;
+    }
+    for (int64_t r = r0 + 1; r < r1; ++r)
+      for (int64_t f = 0; f < F; ++f) seg_max_step(x[r * ldx + f], r, acc[f], best[f]);
+    return;
+  }
+  for (int64_t f = 0; f < F; ++f) acc[f] = 0.0f;
+  float ws = 0.0f;
+  for (int64_t r = r0; r < r1; ++r) {
+    const float* row = x + r * ldx;
+    if (w) {
+      const float wr = w[r];
+      for (int64_t f = 0; f < F; ++f) {
+        const float prod = wr * row[f];
+        acc[f] = acc[f] + prod;
+      }
+      ws = ws + wr;
+    } else {
+      for (int64_t f = 0; f < F; ++f) acc[f] = acc[f] + row[f];
+    }
+  }
+  *wacc = ws;
+}
+
+void check_offsets(int64_t B, int64_t N, const int64_t* offsets) {
+  DGLHIP_CHECK(offsets != nullptr, "offsets is null");
+  DGLHIP_CHECK(offsets[0] == 0, "offsets must start at 0, got " << offsets[0]);
+  for (int64_t s = 0; s < B; ++s)
+    DGLHIP_CHECK(offsets[s + 1] >= offsets[s], "offsets decrease at segment " << s);
+  DGLHIP_CHECK(offsets[B] == N, "offsets end at " << offsets[B] << ", expected the "
+                                                  << N << " rows");
+}
+
+bool seg_op_ok(int op) {
+  return op == DGLHIP_REDUCE_SUM || op == DGLHIP_REDUCE_MAX || op == DGLHIP_REDUCE_MEAN;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dglhip_segment_reduce_host(int reduce_op, int64_t num_segments, int64_t num_rows,
+                               int64_t feat_len, const int64_t* offsets, const float* x,
+                               int64_t ldx, const float* weight, float* y, float* wsum,
+                               int64_t* arg, int num_threads) {
+  API_BEGIN();
+  DGLHIP_CHECK(seg_op_ok(reduce_op), "unknown reduce op " << reduce_op);
+  DGLHIP_CHECK(num_segments >= 0 && num_rows >= 0 && feat_len >= 0, "negative size");
+  check_offsets(num_segments, num_rows, offsets);
+  if (num_segments == 0 || feat_len == 0) return 0;
+  const bool is_max = reduce_op == DGLHIP_REDUCE_MAX;
+  const bool mean = reduce_op == DGLHIP_REDUCE_MEAN;
+  DGLHIP_CHECK(!(is_max && weight), "the max reducer takes no weight");
+  DGLHIP_CHECK(y && (num_rows == 0 || x), "null pointer argument");
+  DGLHIP_CHECK(ldx >= feat_len, "row stride below the row width");
+  DGLHIP_CHECK(!is_max || arg, "the max reducer needs arg");
+  DGLHIP_CHECK(!(mean && weight) || wsum, "the weighted mean needs wsum");
+  const int nt = num_threads > 0 ? num_threads : default_num_threads();
+  const int64_t F = feat_len, C = DGLHIP_SEGMENT_CHUNK;
+  parallel_for(num_segments, nt, [&](int64_t b0, int64_t b1, int) {
+    std::vector<float> part(F);
+    std::vector<int64_t> pbest(is_max ? F : 0);
+    for (int64_t s = b0; s < b1; ++s) {
+      const int64_t beg = offsets[s], end = offsets[s + 1], len = end - beg;
+      float* o = y + s * F;
+      int64_t* oa = is_max ? arg + s * F : nullptr;
+      float wtot = 0.0f;
+      seg_chunk(is_max, F, beg, std::min(end, beg + C), x, ldx, weight, o, &wtot, oa);
+      for (int64_t p = beg + C; p < end; p += C) {
+        float wp = 0.0f;
+        seg_chunk(is_max, F, p, std::min(end, p + C), x, ldx, weight, part.data(), &wp,
+                  pbest.data());
+        if (is_max) {
+          for (int64_t f = 0; f < F; ++f) seg_max_step(part[f], pbest[f], o[f], oa[f]);
+        } else {
+          for (int64_t f = 0; f < F; ++f) o[f] = o[f] + part[f];
+          wtot = wtot + wp;
+        }
+      }
+      if (mean) {
+        const float d = weight ? wtot : static_cast<float>(len > 1 ? len : 1);
+        for (int64_t f = 0; f < F; ++f) o[f] = o[f] / d;
+      }
+      if (weight && wsum) wsum[s] = wtot;
+    }
+  }, num_rows * feat_len > 32768 ? 2 : num_segments + 1);
+  API_END();
+}
+
+int dglhip_segment_reduce_bwd_host(int reduce_op, int64_t num_segments, int64_t num_rows,
+                                   int64_t feat_len, const int64_t* offsets, const float* dy,
+                                   const float* x, int64_t ldx, const float* weight,
+                                   const float* y, const float* wsum, const int64_t* arg,
+                                   float* dx, float* dw, int num_threads) {
+  API_BEGIN();
+  DGLHIP_CHECK(seg_op_ok(reduce_op), "unknown reduce op " << reduce_op);
+  DGLHIP_CHECK(num_segments >= 0 && num_rows >= 0 && feat_len >= 0, "negative size");
+  check_offsets(num_segments, num_rows, offsets);
+  if (num_rows == 0 || feat_len == 0) return 0;
+  const bool is_max = reduce_op == DGLHIP_REDUCE_MAX;
+  const bool mean = reduce_op == DGLHIP_REDUCE_MEAN;
+  const bool wmean = mean && weight;
+  DGLHIP_CHECK(!(is_max && weight), "the max reducer takes no weight");
+  DGLHIP_CHECK(dy && dx, "null pointer argument");
+  DGLHIP_CHECK(!is_max || arg, "the max reducer needs arg");
+  DGLHIP_CHECK(!wmean || (wsum && (!dw || y)), "the weighted mean needs wsum and y");
+  DGLHIP_CHECK(!dw || (weight && x && ldx >= feat_len), "dw needs weight and x");
+  const int nt = num_threads > 0 ? num_threads : default_num_threads();
+  const int64_t F = feat_len;
+  parallel_for(num_segments, nt, [&](int64_t b0, int64_t b1, int) {
+    std::vector<float> g(F);
+    for (int64_t s = b0; s < b1; ++s) {
+      const int64_t beg = offsets[s], end = offsets[s + 1], len = end - beg;
+      if (len == 0) continue;
+      float corr = 0.0f;  // the weighted mean's gradient through its divisor
+      for (int64_t f = 0; f < F; ++f) {
+        float v = dy[s * F + f];
+        if (wmean) v = v / wsum[s];
+        else if (mean) v = v / static_cast<float>(len);
+        g[f] = v;
+        if (wmean && dw) corr += v * y[s * F + f];
+      }
+      for (int64_t i = beg; i < end; ++i) {
+        float* o = dx + i * F;
+        if (is_max) {
+          for (int64_t f = 0; f < F; ++f) o[f] = arg[s * F + f] == i ? g[f] : 0.0f;
+        } else if (weight) {
+          const float wr = weight[i];
+          for (int64_t f = 0; f < F; ++f) o[f] = g[f] * wr;
+        } else {
+          for (int64_t f = 0; f < F; ++f) o[f] = g[f];
+        }
+        if (dw) {
+          float dot = 0.0f;
+          for (int64_t f = 0; f < F; ++f) dot += g[f] * x[i * ldx + f];
+          dw[i] = dot - corr;
+        }
+      }
+    }
+  }, num_rows * feat_len > 32768 ? 2 : num_segments + 1);
+  API_END();
+}
+
+}  // extern "C"

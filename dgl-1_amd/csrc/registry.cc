@@ -181,6 +181,57 @@ void register_kernel_functions() {
     // a plan made for this call owns arrays the enqueued launches read
     if (own && dev) DGLHIP_CHECK(hipStreamSynchronize(s) == hipSuccess, "stream synchronize");
   });
+  // (reduce, offsets, x, weight|null, y, wsum|null, arg|null, stream): the
+  // segment reduction y[s] = REDUCE x[offsets[s] : offsets[s+1]] of
+  // dglhip_segment_reduce_host / _device by the tensors' device; x is
+  // [rows, feat] (rows may sit at a padded stride), y [segments, feat]. The
+  // device form's workspace is taken from and returned to the stream's pool.
+  register_global("dglhip._CAPI_SegmentReduce", [](const Args& a, RetValue*) {
+    const int red = static_cast<int>(a.i64(0));
+    auto* offsets = a.tensor(1);
+    auto* x = a.tensor(2);
+    auto* w = a.tensor(3, true);
+    auto* y = a.tensor(4);
+    auto* wsum = a.tensor(5, true);
+    auto* arg = a.tensor(6, true);
+    void* stream = a.size() > 7 ? a.handle(7) : nullptr;
+    same_device(y, {offsets, x, w, wsum, arg});
+    DGLHIP_CHECK(y->ndim == 2 && x->ndim == 2, "x and y must be 2-D [rows, feat]");
+    const int64_t B = y->shape[0], F = y->shape[1], N = x->shape[0];
+    DGLHIP_CHECK(x->shape[1] == F, "x and y differ in feature length");
+    DGLHIP_CHECK(numel(offsets) == B + 1, "offsets length must be segments+1");
+    DGLHIP_CHECK(!w || numel(w) == N, "weight length must be the number of rows");
+    DGLHIP_CHECK(!wsum || numel(wsum) == B, "wsum length must be the number of segments");
+    DGLHIP_CHECK(!arg || numel(arg) == B * F, "arg must be [segments, feat]");
+    int64_t ldx = F;
+    if (x->strides && N > 1 && F > 0 && x->strides[1] == 1 && x->strides[0] > F) {
+      ldx = x->strides[0];
+    } else {
+      check_compact(x, "x");
+    }
+    check_compact(y, "y");
+    const float* xp = reinterpret_cast<const float*>(static_cast<const char*>(x->data) +
+                                                     x->byte_offset);
+    DGLHIP_CHECK(x->dtype_code == 2 && x->dtype_bits == 32, "x must be float32");
+    const bool dev = y->device_type == kDeviceROCM;
+    DGLHIP_CHECK(dev || y->device_type == kDeviceCPU, "unsupported device type "
+                                                         << y->device_type);
+    if (!dev) {
+      throw_last(dglhip_segment_reduce_host(red, B, N, F, I64(offsets, "offsets"), xp, ldx,
+                                            F32(w, "weight"), F32(y, "y"), F32(wsum, "wsum"),
+                                            I64(arg, "arg"), 0));
+      return;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream_or_current(stream, y));
+    const int64_t bytes = dglhip_segment_reduce_workspace_bytes(red, B, N, F);
+    void* ws = nullptr;
+    if (bytes > 0) DGLHIP_CHECK(hipMallocAsync(&ws, bytes, s) == hipSuccess, "workspace allocation");
+    const int rc = dglhip_segment_reduce_device(red, B, N, F, I64(offsets, "offsets"), xp, ldx,
+                                                F32(w, "weight"), F32(y, "y"), F32(wsum, "wsum"),
+                                                I64(arg, "arg"), -1, ws, s);
+    if (ws) (void)hipFreeAsync(ws, s);
+    throw_last(rc);
+  });
   // (indptr, indices, num_cols, row_order|null, stream) -> plan handle
   register_global("dglhip._CAPI_SpmmPlanCreate", [](const Args& a, RetValue* rv) {
     auto* indptr = a.tensor(0);

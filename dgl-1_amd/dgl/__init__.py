@@ -15,6 +15,9 @@ from . import init  # noqa: F401
 from . import kernel  # noqa: F401
 from .base import ALL, DGLError  # noqa: F401
 from .graph import DGLGraph  # noqa: F401
+from .batched_graph import (BatchedDGLGraph, batch, unbatch, split,  # noqa: F401
+                            sum_nodes, sum_edges, mean_nodes, mean_edges,
+                            max_nodes, max_edges)
 from .udf import EdgeBatch, NodeBatch  # noqa: F401
 from .runtime import ir  # noqa: F401
 from . import nn  # noqa: F401

@@ -211,6 +211,15 @@ def _load():
                                                      _c_i64, _vp, _vp, _vp]),
         "dglhip_node_linear_dgrad_workspace_floats": (_c_i64, [_c_i64]),
         "dglhip_div_rows_device": (_c_int, [_c_i64, _c_i64, _vp, _c_i64, _vp, _vp, _c_i64, _vp]),
+        "dglhip_segment_reduce_workspace_bytes": (_c_i64, [_c_int, _c_i64, _c_i64, _c_i64]),
+        "dglhip_segment_reduce_device": (_c_int, [_c_int, _c_i64, _c_i64, _c_i64, _vp, _vp, _c_i64,
+                                                  _vp, _vp, _vp, _vp, _c_i64, _vp, _vp]),
+        "dglhip_segment_reduce_host": (_c_int, [_c_int, _c_i64, _c_i64, _c_i64, _vp, _vp, _c_i64,
+                                                _vp, _vp, _vp, _vp, _c_int]),
+        "dglhip_segment_reduce_bwd_device": (_c_int, [_c_int, _c_i64, _c_i64, _c_i64] + [_vp] * 3 +
+                                             [_c_i64] + [_vp] * 7),
+        "dglhip_segment_reduce_bwd_host": (_c_int, [_c_int, _c_i64, _c_i64, _c_i64] + [_vp] * 3 +
+                                           [_c_i64] + [_vp] * 6 + [_c_int]),
         "dglhip_xent_workspace_floats": (_c_int, []),
         "dglhip_xent_fwd_device": (_c_int, [_c_i64, _c_i64, _vp, _c_i64, _vp, _vp, _vp, _vp, _vp]),
         "dglhip_xent_bwd_device": (_c_int, [_c_i64, _c_i64, _vp, _c_i64, _vp, _vp, _vp, _vp,

@@ -16,13 +16,15 @@ built from it per device (kernel.from_coo); all are dropped on mutation.
 """
 from __future__ import absolute_import
 
+import ctypes
+
 import numpy as np
 import torch
 
 from . import _ffi, kernel
 from .base import DGLError
 
-__all__ = ["GraphIndex", "create_graph_index"]
+__all__ = ["GraphIndex", "create_graph_index", "disjoint_union", "disjoint_partition"]
 
 _CAPI = _ffi.CAPINamespace("graph_index")
 
@@ -287,6 +289,27 @@ def _from_edges(n, src, dst, multigraph, readonly):
     gi.add_nodes(n)
     gi.add_edges(src, dst)
     return gi
+
+
+def disjoint_union(graphs):
+    """One index holding the given indices side by side, node and edge ids
+    offset by the running sizes (graph_index.py:895-917): one
+    ``_CAPI_DGLDisjointUnion`` call over the list of handles."""
+    graphs = list(graphs)
+    handles = (ctypes.c_void_p * max(len(graphs), 1))(*[g._handle for g in graphs])
+    h = _call("_CAPI_DGLDisjointUnion", ("handle", ctypes.addressof(handles)), len(graphs))
+    return GraphIndex(any(g.is_multigraph() for g in graphs), False, handle=h)
+
+
+def disjoint_partition(graph, num_or_size_splits):
+    """The inverse of :func:`disjoint_union` (graph_index.py:919-947): the
+    parts of ``graph`` with the given node counts (a list / tensor of sizes),
+    or an int number of equal parts; edges may not cross parts."""
+    if isinstance(num_or_size_splits, (int, np.integer)):
+        hs = _call("_CAPI_DGLDisjointPartitionByNum", graph._h(), int(num_or_size_splits))
+    else:
+        hs = _call("_CAPI_DGLDisjointPartitionBySizes", graph._h(), _as_i64(num_or_size_splits))
+    return [GraphIndex(graph.is_multigraph(), False, handle=int(h)) for h in hs.tolist()]
 
 
 def create_graph_index(graph_data=None, multigraph=False, readonly=False):

@@ -417,6 +417,71 @@ int dglhip_node_epilogue_bwd_device(int64_t num_rows, int64_t feat_len, const fl
                                     float* dx, float* col_partial, void* stream);
 
 /* ------------------------------------------------------------------------ */
+/* Segment reduction (csrc/segment_reduce.hip): the readout of a batched     */
+/* graph, the reference's sum_nodes / mean_nodes / max_nodes and their edge  */
+/* twins (python/dgl/batched_graph.py:362-766), which it delegates to        */
+/* scatter_add_ and a loop of torch.max per graph.                           */
+/*   y[s, :] = REDUCE over rows i in [offsets[s], offsets[s+1]) of x[i, :]   */
+/* x: float32 rows of feat_len columns at stride ldx >= feat_len; offsets:   */
+/* int64[num_segments + 1], non-decreasing, offsets[0] = 0,                  */
+/* offsets[num_segments] = num_rows; weight: float32[num_rows] or NULL.      */
+/* reduce_op is DGLHIP_REDUCE_SUM, _MEAN or _MAX (no weight with _MAX).      */
+/* - sum: a float32 chain from +0.0f in row order per column; with a weight  */
+/*   each term is the rounded product weight[i] * x[i, f] (no fma).          */
+/* - mean: that chain / float(max(rows, 1)); weighted: the chain of the      */
+/*   products / the chain of the weights (an empty segment gives NaN).       */
+/*   wsum[s] (float32[num_segments], NULL only without a weight or for the   */
+/*   sum) receives the chain of the weights.                                 */
+/* - max: elementwise, NaN propagates; arg[s, f] (int64) is the first row    */
+/*   attaining it or the first NaN; an empty segment gives 0.0 and -1.       */
+/* A segment of more than DGLHIP_SEGMENT_CHUNK rows is cut into chunks of    */
+/* that many rows from its start: each chunk is a chain from zero and the    */
+/* chunk results are added (max: compared, the earlier chunk winning ties)   */
+/* in chunk order. Host and device run the same chains: identical bits.      */
+/* ------------------------------------------------------------------------ */
+#define DGLHIP_SEGMENT_CHUNK 1024
+/* Bytes of the device form's workspace (0: none needed). */
+int64_t dglhip_segment_reduce_workspace_bytes(int reduce_op, int64_t num_segments,
+                                              int64_t num_rows, int64_t feat_len);
+/* Device form: all pointers are device pointers; one launch, plus one that
+ * adds the chunk partials from `workspace` when a segment may be longer than
+ * a chunk. max_segment_rows: the longest segment if the caller knows it from
+ * host-side sizes (<= DGLHIP_SEGMENT_CHUNK skips the chunk work), -1 if not.
+ * No host sync, no allocation, no atomics; out-of-range offsets are clamped
+ * to [0, num_rows], never followed. */
+int dglhip_segment_reduce_device(int reduce_op, int64_t num_segments, int64_t num_rows,
+                                 int64_t feat_len, const int64_t* offsets, const float* x,
+                                 int64_t ldx, const float* weight, float* y, float* wsum,
+                                 int64_t* arg, int64_t max_segment_rows, void* workspace,
+                                 void* stream);
+/* Host form (thread pool). Offsets that do not start at 0, decrease or do not
+ * end at num_rows return -1 with a message. */
+int dglhip_segment_reduce_host(int reduce_op, int64_t num_segments, int64_t num_rows,
+                               int64_t feat_len, const int64_t* offsets, const float* x,
+                               int64_t ldx, const float* weight, float* y, float* wsum,
+                               int64_t* arg, int num_threads);
+/* Backward, one pass over the rows, every dx element written exactly once
+ * (dx: num_rows x feat_len packed; dy, y: num_segments x feat_len packed):
+ * - sum:  dx[i, f] = dy[s, f] (* weight[i]);
+ * - mean: dx[i, f] = dy[s, f] / float(max(rows, 1)); weighted: weight[i] *
+ *   (dy[s, f] / wsum[s]);
+ * - max:  dx[i, f] = arg[s, f] == i ? dy[s, f] : 0.
+ * dw (NULL: not wanted; needs weight and x): dw[i] = sum_f g[s, f] * x[i, f]
+ * with g the (divided) gradient above; the weighted mean subtracts
+ * sum_f g[s, f] * y[s, f], the gradient through its divisor. y and wsum are
+ * the forward's outputs (weighted mean only), arg the max's. */
+int dglhip_segment_reduce_bwd_device(int reduce_op, int64_t num_segments, int64_t num_rows,
+                                     int64_t feat_len, const int64_t* offsets, const float* dy,
+                                     const float* x, int64_t ldx, const float* weight,
+                                     const float* y, const float* wsum, const int64_t* arg,
+                                     float* dx, float* dw, void* stream);
+int dglhip_segment_reduce_bwd_host(int reduce_op, int64_t num_segments, int64_t num_rows,
+                                   int64_t feat_len, const int64_t* offsets, const float* dy,
+                                   const float* x, int64_t ldx, const float* weight,
+                                   const float* y, const float* wsum, const int64_t* arg,
+                                   float* dx, float* dw, int num_threads);
+
+/* ------------------------------------------------------------------------ */
 /* Weighted softmax cross-entropy over node rows (csrc/node_loss.hip): the   */
 /* loss of a full-graph node classifier. No reference counterpart: the       */
 /* reference's examples call torch's F.cross_entropy / nll_loss             */
