@@ -370,11 +370,21 @@ __global__ __launch_bounds__(256) void gspmm_combine_kernel(
 }
 
 // Max-reduce kernel with argmax slot: first slot wins ties (a strict running
-// max over the mailbox, seeded with the first message), 0 / -1 for rows
-// without slots. Same lane mapping as the sum kernel (GROUP lanes per row,
-// VEC features per lane, UNROLL gathers in flight); the compares then run
-// slot by slot in CSR order, so the argmax is the one the sequential
-// reduction picks.
+// max over the mailbox, seeded with the first message), and a NaN message is
+// taken like a larger one and then kept (torch.max: the row's first NaN wins,
+// value and argmax; segment_reduce.hip's max_step is the same rule); 0 / -1
+// for rows without slots. Same lane mapping as the sum kernel (GROUP lanes
+// per row, VEC features per lane, UNROLL gathers in flight); the compares
+// then run slot by slot in CSR order, so the argmax is the one the sequential
+// reduction picks. A NaN running value is never replaced, so a row continued
+// from an earlier source block (prev) keeps the earlier block's NaN.
+// The rule is "best is not NaN, and x is greater or NaN"; !(x <= best) is
+// "greater or unordered", and the mask AND keeps it two compares without the
+// per-element branches a short-circuit && / || compiles to.
+__device__ __forceinline__ bool max_takes(float x, float best) {
+  return (best == best) & !(x <= best);
+}
+
 template <int VEC, int UNROLL, int MSG, int EM, bool USE_EID>
 __device__ __forceinline__ void max_row(int64_t row, int gl, int group, int64_t beg,
                                         int64_t end, int64_t F, int64_t elen,
@@ -424,7 +434,7 @@ __device__ __forceinline__ void max_row(int64_t row, int gl, int group, int64_t 
         for (int i = 0; i < VEC; ++i) {
           const float xi = reinterpret_cast<const float*>(&x)[i];
           float& bi = reinterpret_cast<float*>(&best)[i];
-          if (xi > bi) { bi = xi; arg[i] = k + j; }
+          if (max_takes(xi, bi)) { bi = xi; arg[i] = k + j; }
         }
       }
     }
@@ -442,7 +452,7 @@ __device__ __forceinline__ void max_row(int64_t row, int gl, int group, int64_t 
           for (int i = 0; i < VEC; ++i) {
             const float xi = reinterpret_cast<const float*>(&x)[i];
             float& bi = reinterpret_cast<float*>(&best)[i];
-            if (xi > bi) { bi = xi; arg[i] = k + j; }
+            if (max_takes(xi, bi)) { bi = xi; arg[i] = k + j; }
           }
         }
       }

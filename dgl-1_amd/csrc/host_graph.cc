@@ -269,7 +269,8 @@ int dglhip_gspmm_host(int msg_op, int reduce_op, int64_t num_rows,
             if (msg_op == DGLHIP_MSG_COPY_U) x = ufeat[int64_t(indices[k]) * F + f];
             else if (msg_op == DGLHIP_MSG_COPY_E) x = er[f / dpe];
             else x = ufeat[int64_t(indices[k]) * F + f] * er[f / dpe];
-            if (arg < 0 || x > best) { best = x; arg = k; }
+            // torch.max: the first maximum, or the first NaN, which is then kept
+            if (arg < 0 || (!(best != best) && (x > best || x != x))) { best = x; arg = k; }
           }
           o[f] = arg < 0 ? 0.0f : best;
           if (arg_out) arg_out[r * F + f] = arg;
@@ -296,7 +297,7 @@ int dglhip_gspmm_host(int msg_op, int reduce_op, int64_t num_rows,
         const float inv = static_cast<float>(t - s);
         for (int64_t f = 0; f < F; ++f) o[f] = o[f] / inv;
       }
-      if (add_mean && t > s) {
+      if (add_mean) {  // rows without in-edges too: out + 0.0f (-0.0 becomes +0.0)
         float* dst = out + r * F;
         for (int64_t f = 0; f < F; ++f) dst[f] = dst[f] + o[f];
       }

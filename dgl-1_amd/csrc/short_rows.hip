@@ -18,7 +18,7 @@
 // routes only short rows here). The chain per output element is the main
 // kernel's (0 + x_0 + x_1 + ..., or continued from out for sum_accum), so
 // the results are bit-identical. MAXD = 0: rows without slots, R of them per
-// wave, stored as zeros.
+// wave, stored as zeros (mean_accum: out + 0.0f; sum_accum never lists them).
 
 #include "gspmm_impl.h"
 

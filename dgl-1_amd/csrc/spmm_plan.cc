@@ -81,6 +81,11 @@ inline bool accum(int red) {
   return red == DGLHIP_REDUCE_SUM_ACCUM || red == DGLHIP_REDUCE_MEAN_ACCUM;
 }
 
+// Rows without slots are left out of a launch only where keeping out is the
+// definition (the chain continued from out). out + mean adds the mean's +0.0
+// to them, which turns a -0.0 in out into +0.0.
+inline bool skips_empty(int red) { return red == DGLHIP_REDUCE_SUM_ACCUM; }
+
 }  // namespace
 
 SpmmPolicy spmm_policy() {
@@ -935,7 +940,7 @@ Decision decide(SpmmPlan& plan, const RunArgs& a, hipStream_t s) {
     d.ws_pad = align256(a.urows * d.ld * 4);
   }
   if (d.split) {
-    const bool skip = accum(a.red);
+    const bool skip = skips_empty(a.red);
     const int64_t chunk = p.row_split < 0 ? -1 : d.split;
     const SplitPlan& sp = plan.split_plan(d.split, skip, chunk, s);
     d.ws_partial = align256(sp.n_chunks * a.F * 4);
@@ -956,7 +961,7 @@ struct Workspace {
 void short_rows(SpmmPlan& plan, const RunArgs& a, const Tiers& t, const void* uf, int64_t ld,
                 hipStream_t s) {
   for (const Tier& tier : t.tiers) {
-    if (tier.maxd == 0 && accum(a.red)) continue;  // nothing to add
+    if (tier.maxd == 0 && skips_empty(a.red)) continue;  // nothing to add
     DGLHIP_CHECK(dglhip_gspmm_short_rows_device(
                      a.msg, a.red, tier.n, a.F, tier.maxd, plan.num_rows(),
                      tier.rows.data<int32_t>(),
@@ -1076,7 +1081,7 @@ void run_planned(SpmmPlan& plan, const RunArgs& a, const Decision& d, void* work
     if (a.emode == DGLHIP_EDGE_BY_MAP) eid = a.erow;
     else if (!plan.eid_identity(a.erow, s)) eid = a.erow;
   }
-  const bool skip = accum(a.red);  // empty rows: nothing to add
+  const bool skip = skips_empty(a.red);  // empty rows: nothing to add
   const bool tiered = p.short_rows && copies_u(a.msg) &&
                       (a.red == DGLHIP_REDUCE_SUM || a.red == DGLHIP_REDUCE_MEAN || accum(a.red));
   const int64_t ld = d.ld;

@@ -207,9 +207,9 @@ __global__ __launch_bounds__(256) void div_degree_kernel(int64_t R, int64_t F,
   for (int64_t f = threadIdx.x & 63; f < F; f += 64) o[f] = o[f] / div;
 }
 
-// out[r] = out[r] + sums[r] / deg r for rows with in-edges (the one-launch
-// mean_add store: the chain, divided when deg > 1, added to out; rows without
-// in-edges keep out)
+// out[r] = out[r] + sums[r] / deg r (the one-launch mean_add store: the
+// chain, divided when deg > 1, added to out; rows without in-edges add the
+// mean's +0.0, so a -0.0 in out becomes +0.0 as in out + mean)
 __global__ __launch_bounds__(256) void add_mean_kernel(int64_t R, int64_t F,
                                                        const int64_t* __restrict__ indptr,
                                                        const float* __restrict__ sums,
@@ -217,12 +217,12 @@ __global__ __launch_bounds__(256) void add_mean_kernel(int64_t R, int64_t F,
   const int64_t r = block_linear() * 4 + (threadIdx.x >> 6);
   if (r >= R) return;
   const int64_t d = indptr[r + 1] - indptr[r];
-  if (d == 0) return;
   const float div = static_cast<float>(d);
   const float* sr = sums + r * F;
   float* o = out + r * F;
   for (int64_t f = threadIdx.x & 63; f < F; f += 64) {
-    const float m = d > 1 ? sr[f] / div : sr[f];
+    // a row without in-edges: out + 0.0f, whatever its row of sums holds
+    const float m = d > 1 ? sr[f] / div : (d == 1 ? sr[f] : 0.0f);
     o[f] = o[f] + m;
   }
 }

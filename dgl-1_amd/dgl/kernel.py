@@ -1332,8 +1332,8 @@ class _MeanAddInto(torch.autograd.Function):
 def gspmm_mean_add(adj, ufeat, out):
     """out <- out + mean over in-edges of ufeat[src] (copy_u + mean), in place
     and differentiable: the value of ``out + gspmm(adj, "copy_u", "mean",
-    ufeat)`` bit for bit (a sum of two terms; rows without in-edges keep their
-    value), with the addition in the aggregation's own store instead of a pass
+    ufeat)`` bit for bit (a sum of two terms; rows without in-edges store
+    out + 0.0, so a -0.0 there becomes +0.0), with the addition in the aggregation's own store instead of a pass
     over both tensors (GraphSAGE's fc_self(h) + mean(fc_neigh(h)),
     nn.pytorch.sage_dense). ``out``: contiguous float32 (num_rows, F) on the
     features' device; ufeat may be row-padded (F columns of a wider row)."""

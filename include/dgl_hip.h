@@ -734,7 +734,8 @@ int dglhip_set_sweep_unroll(int unroll);
  * earlier slots' max) and a row with an empty range is left as it is; the
  * first range of a row starts it. Launches over the rows' source-block
  * sub-ranges in block order give the one-launch values and, ties included,
- * the one-launch argmax (strict > keeps the earliest slot). */
+ * the one-launch argmax (strict > keeps the earliest slot; a NaN is taken
+ * like a larger value and then kept, so the first NaN wins: torch.max). */
 int dglhip_gspmm_max_ranges_device(int msg_op, int64_t num_rows, int64_t feat_len,
                                    const int64_t* indptr, const int64_t* row_beg,
                                    const int64_t* row_end, int accumulate,

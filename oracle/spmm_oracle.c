@@ -90,7 +90,8 @@ void oracle_spmm_csr(int64_t num_rows, int64_t F, const int64_t* indptr,
 }
 
 /* Degree-bucketing max over each row's mailbox of messages m[pos[k], :]
- * (torch.max over dim 1 is exact); empty rows = 0 (zero initializer). */
+ * (torch.max over dim 1 is exact, and returns NaN for a column that holds
+ * one); empty rows = 0 (zero initializer). */
 void oracle_max_mailbox(int64_t num_rows, int64_t F, const int64_t* indptr,
                         const int64_t* pos, const float* msg, float* out) {
   for (int64_t r = 0; r < num_rows; ++r) {
@@ -103,7 +104,8 @@ void oracle_max_mailbox(int64_t num_rows, int64_t F, const int64_t* indptr,
     for (int64_t k = indptr[r] + 1; k < indptr[r + 1]; ++k)
       for (int64_t f = 0; f < F; ++f) {
         const float x = msg[pos[k] * F + f];
-        if (x > o[f]) o[f] = x;
+        /* torch.max: the first maximum, or the first NaN, which is kept */
+        if (!(o[f] != o[f]) && (x > o[f] || x != x)) o[f] = x;
       }
   }
 }

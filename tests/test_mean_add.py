@@ -26,7 +26,14 @@ def _graph(rng, n, nnz, skew):
 
 
 def _check(adj, h, base, dev):
-    """Fused vs unfused: values and both gradients, bit for bit."""
+    """Fused vs unfused: values (sign bits too: ``==`` takes -0.0 for +0.0)
+    and both gradients, bit for bit. ``base`` gets -0.0 entries, whole rows of
+    them on rows without in-edges, where out + mean is -0.0 + 0.0 = +0.0."""
+    base = base.clone()
+    empty = (adj.fwd.degrees() == 0).nonzero()[:, 0]
+    assert empty.numel() > 1
+    base[empty[::2]] = -0.0
+    base[::7, 0] = -0.0
     h1 = h.detach().clone().requires_grad_(True)
     ref = base + kernel.gspmm(adj, "copy_u", "mean", h1)
     g = torch.randn(ref.shape, generator=torch.Generator().manual_seed(3)).to(dev)
@@ -36,6 +43,8 @@ def _check(adj, h, base, dev):
     out = kernel.gspmm_mean_add(adj, h2, b2.clone())
     out.backward(g)
     assert torch.equal(out.detach(), ref.detach())
+    assert torch.equal(torch.signbit(out.detach()), torch.signbit(ref.detach()))
+    assert not torch.signbit(out.detach()[empty[::2]]).any()
     assert torch.equal(h2.grad, h1.grad)
     assert torch.equal(b2.grad, g)
 

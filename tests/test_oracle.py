@@ -110,3 +110,35 @@ def test_reddit_rows_fixture(golden):
     ip, ix, pos = O.coo_to_csr(n, dst, src)
     assert P.digest(O.spmm_csr(ip, ix, pos, H, num_threads=8)) == str(c["sha_copy_out"])
     assert P.digest(O.spmm_csr(ip, ix, pos, H, W, num_threads=8)) == str(c["sha_mul_out"])
+
+
+def test_max_mailbox_is_torch_max_with_nans():
+    """The oracle's max is pinned to torch, not to the kernels: per row
+    torch.max(mailbox, 0) on the CPU, whose column is NaN once it holds one
+    (first, in the middle, last, twice), with infinities and zeros of both
+    signs among the messages; rows without messages read +0.0."""
+    import torch
+    rng = np.random.default_rng(21)
+    n, m, F = 40, 400, 6
+    row = rng.integers(0, n - 5, m)  # the last rows stay empty
+    msg = rng.integers(-3, 4, (m, F)).astype(np.float32)
+    msg[rng.random((m, F)) < 0.05] = np.nan
+    msg[rng.random((m, F)) < 0.05] = np.inf
+    msg[rng.random((m, F)) < 0.05] = -np.inf
+    msg[rng.random((m, F)) < 0.05] = -0.0
+    first = np.array([np.nonzero(row == r)[0][0] for r in range(3)])
+    last = np.array([np.nonzero(row == r)[0][-1] for r in range(3, 6)])
+    msg[first, 0] = np.nan
+    msg[last, 1] = np.nan
+    got = O.max_mailbox(n, row, msg)
+    late = 0
+    for r in range(n):
+        es = np.nonzero(row == r)[0]
+        want = torch.max(torch.from_numpy(msg[es]), 0)[0].numpy() if len(es) else \
+            np.zeros(F, np.float32)
+        assert np.array_equal(np.isnan(got[r]), np.isnan(want)), r
+        ok = ~np.isnan(want)
+        assert np.array_equal(got[r][ok].view(np.int32), want[ok].view(np.int32)), r
+        if len(es):
+            late += int((np.isnan(msg[es[1:]]).any(0) & ~np.isnan(msg[es[0]])).sum())
+    assert late > 20 and np.isnan(got).sum() >= late
