@@ -18,6 +18,7 @@ from .graph import DGLGraph  # noqa: F401
 from .batched_graph import (BatchedDGLGraph, batch, unbatch, split,  # noqa: F401
                             sum_nodes, sum_edges, mean_nodes, mean_edges,
                             max_nodes, max_edges)
+from .subgraph import DGLSubGraph  # noqa: F401
 from .udf import EdgeBatch, NodeBatch  # noqa: F401
 from .runtime import ir  # noqa: F401
 from . import nn  # noqa: F401

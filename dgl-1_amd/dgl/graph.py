@@ -19,6 +19,7 @@ from .base import ALL, DGLError, is_all
 from .frame import Frame
 from .graph_index import create_graph_index
 from .runtime import scheduler
+from .udf import EdgeBatch, LazyDict, NodeBatch
 from .view import EdgeView, NodeView
 
 __all__ = ["DGLGraph"]
@@ -460,6 +461,73 @@ class DGLGraph(object):
     def sparse_adjacency(self, ctx):
         """The engine's cached g-SpMM adjacency (kernel.SparseAdj) on ``ctx``."""
         return self._graph.adjacency(ctx)
+
+    # -- subgraphs and filters (graph.py:2600-2719, 2800-2931) ------------------
+    def subgraph(self, nodes):
+        """The subgraph induced by ``nodes``: subgraph node ``i`` is
+        ``nodes[i]`` and the edges are those of the parent with both ends in
+        the set (``parent_nid`` / ``parent_eid`` map back). Features are not
+        copied; see :meth:`DGLSubGraph.copy_from_parent`.
+
+        Ids given as a tensor on a ROCm device, on a mutable parent, are
+        induced there by a HIP kernel over the cached source-major adjacency:
+        the ids, the structure and the parent ids stay on the device, the
+        result equals the host answer element for element, and ids that are
+        out of range or repeated raise DGLError. Lists, arrays and host
+        tensors, and every readonly parent (sorted ids), go through the native
+        index.
+
+        >>> g = dgl.DGLGraph(); g.add_nodes(5)
+        >>> g.add_edges([0, 1, 2, 3, 4], [1, 2, 3, 4, 0])
+        >>> sg = g.subgraph([0, 1, 4])
+        >>> sg.edges(), sg.parent_nid, sg.parent_eid
+        ((tensor([0, 2]), tensor([1, 0])), tensor([0, 1, 4]), tensor([0, 4]))
+        """
+        from .subgraph import DGLSubGraph
+        if isinstance(nodes, torch.Tensor) and nodes.is_cuda and not self.is_readonly:
+            sgi = self._graph.node_subgraph_device(nodes)
+        else:
+            sgi = self._graph.node_subgraph(utils.toindex(nodes))
+        return DGLSubGraph(self, sgi.induced_nodes, sgi.induced_edges, sgi)
+
+    def subgraphs(self, nodes):
+        """One :meth:`subgraph` per node set of the list ``nodes``."""
+        return [self.subgraph(v) for v in nodes]
+
+    def edge_subgraph(self, edges):
+        """The subgraph of the given edge ids: subgraph edge ``i`` is
+        ``edges[i]``; its nodes are the edges' end points, numbered by first
+        appearance."""
+        from .subgraph import DGLSubGraph
+        sgi = self._graph.edge_subgraph(utils.toindex(edges))
+        return DGLSubGraph(self, sgi.induced_nodes, sgi.induced_edges, sgi)
+
+    def filter_nodes(self, predicate, nodes=ALL):
+        """Ids of the nodes that satisfy ``predicate``, a function of a
+        :class:`~dgl.udf.NodeBatch` returning a 1-D boolean mask. The ids are
+        on the mask's device, so ``g.subgraph(g.filter_nodes(pred))`` over
+        device features stays there."""
+        if is_all(nodes):
+            v = torch.arange(self.number_of_nodes(), dtype=torch.int64)
+            mask = predicate(NodeBatch(self, v, self.get_n_repr()))
+            return torch.nonzero(mask).reshape(-1)
+        v = utils.toindex(nodes)
+        mask = predicate(NodeBatch(self, v, self.get_n_repr(v)))
+        return v.to(mask.device)[mask]
+
+    def filter_edges(self, predicate, edges=ALL):
+        """Ids of the edges that satisfy ``predicate``, a function of an
+        :class:`~dgl.udf.EdgeBatch` returning a 1-D boolean mask (``edges``
+        as for :meth:`send`); on the mask's device."""
+        u, v, eid = self._edge_triplet(edges)
+        nf = self._node_frame
+        src = LazyDict(lambda k: nf[k].index_select(0, u.to(nf[k].device)), nf.keys())
+        dst = LazyDict(lambda k: nf[k].index_select(0, v.to(nf[k].device)), nf.keys())
+        edata = self.get_e_repr() if is_all(edges) else self.get_e_repr(eid)
+        mask = predicate(EdgeBatch(self, (u, v, eid), src, edata, dst))
+        if is_all(edges):
+            return torch.nonzero(mask).reshape(-1)
+        return eid.to(mask.device)[mask]
 
     def __repr__(self):
         return ("DGLGraph(num_nodes={n}, num_edges={m},\n         ndata_schemes={ns}\n"

@@ -24,19 +24,25 @@ import torch
 from . import _ffi, kernel
 from .base import DGLError
 
-__all__ = ["GraphIndex", "create_graph_index", "disjoint_union", "disjoint_partition"]
+__all__ = ["GraphIndex", "SubgraphIndex", "create_graph_index", "disjoint_union",
+           "disjoint_partition", "map_to_subgraph_nid"]
 
 _CAPI = _ffi.CAPINamespace("graph_index")
 
 
 def _as_i64(x):
     if isinstance(x, torch.Tensor):
+        if x.numel() == 0:  # (an empty view may carry any stride)
+            return torch.zeros(0, dtype=torch.int64)
         return x.detach().to(dtype=torch.int64, device="cpu").reshape(-1).contiguous()
     if isinstance(x, slice):
         return torch.arange(x.start or 0, x.stop, x.step or 1, dtype=torch.int64)
     if isinstance(x, (int, np.integer)):
         return torch.tensor([int(x)], dtype=torch.int64)
-    return torch.as_tensor(np.asarray(x, dtype=np.int64)).reshape(-1).contiguous()
+    arr = np.asarray(x, dtype=np.int64)
+    if arr.size == 0:
+        return torch.zeros(0, dtype=torch.int64)
+    return torch.as_tensor(arr).reshape(-1).contiguous()
 
 
 def _triple(f):
@@ -263,6 +269,40 @@ class GraphIndex(object):
     def has_edges_between(self, u, v):
         return _call("_CAPI_DGLGraphHasEdgesBetween", self._h(), _as_i64(u), _as_i64(v))
 
+    # -- subgraphs (graph_index.py:483-535) ------------------------------------
+    def node_subgraph(self, v):
+        """The subgraph induced by the nodes ``v`` (``_CAPI_DGLGraphVertexSubgraph``):
+        subgraph node ``i`` is ``v[i]``. A mutable index lists the out-edges of
+        ``v[0]``, ``v[1]``, ... in edge-id order that end inside the set; an
+        immutable one takes a sorted ``v`` and numbers the edges by CSR slot."""
+        f = _call("_CAPI_DGLGraphVertexSubgraph", self._h(), _as_i64(v))
+        return SubgraphIndex(self, f(1), f(2), handle=f(0))
+
+    def node_subgraphs(self, vs):
+        """One :meth:`node_subgraph` per node set of the list ``vs``."""
+        return [self.node_subgraph(v) for v in vs]
+
+    def edge_subgraph(self, e):
+        """The subgraph of the edges ``e`` (``_CAPI_DGLGraphEdgeSubgraph``):
+        subgraph edge ``i`` is ``e[i]``, nodes are numbered by first appearance."""
+        f = _call("_CAPI_DGLGraphEdgeSubgraph", self._h(), _as_i64(e))
+        return SubgraphIndex(self, f(1), f(2), handle=f(0))
+
+    def node_subgraph_device(self, v):
+        """:meth:`node_subgraph` of a mutable index for ids ``v`` on a ROCm
+        device, extracted there from the source-major CSR of the cached
+        adjacency (kernel.induced_subgraph); the same nodes, edges and order as
+        the native index gives. Ids outside the graph or listed twice raise."""
+        if self._readonly:
+            raise DGLError("the device route needs a mutable parent index")
+        if torch.cuda.is_current_stream_capturing():  # before anything is launched
+            raise DGLError("subgraph() of device ids reads the subgraph's size on the host: "
+                           "it cannot run while a stream is being captured")
+        adj = self.adjacency(v.device)
+        src, dst, eid = kernel.induced_subgraph(adj.bwd, v)
+        nid = v.detach().to(torch.int64).reshape(-1)
+        return SubgraphIndex(self, nid, eid, device_coo=(nid.numel(), src, dst))
+
     # -- pickling (graph_index.py:35-59): rebuildable from (n, multigraph, readonly, src, dst)
     def __getstate__(self):
         return (self._n, self._multigraph, self._readonly, self.src().numpy().copy(),
@@ -273,6 +313,118 @@ class GraphIndex(object):
         g = _from_edges(n, torch.as_tensor(src), torch.as_tensor(dst), multi, ro)
         self.__dict__.update(g.__dict__)
         g._handle = None  # ownership moved to self
+
+
+class SubgraphIndex(GraphIndex):
+    """The index of a subgraph (graph_index.py:810-890): a read-only structure
+    that remembers which parent nodes and edges it was induced from.
+
+    Made either from the handle the native index returned, or from the edge
+    list ``device_coo = (n, src, dst)`` a device extraction left on the GPU
+    (GraphIndex.node_subgraph_device). In the second form the sizes and the
+    g-SpMM CSRs on that device come straight from the device arrays, and the
+    native index is only built, from one download of the edge list, when a
+    query needs it (:attr:`has_native_index`)."""
+
+    def __init__(self, parent, induced_nodes, induced_edges, handle=None, device_coo=None):
+        # not GraphIndex.__init__: that creates a native index at once
+        self._handle = handle
+        self._multigraph = parent.is_multigraph()
+        self._readonly = parent.is_readonly()
+        self._cache = {}
+        self._parent = parent
+        self._induced_nodes = induced_nodes
+        self._induced_edges = induced_edges
+        self._dev_coo = None
+        if handle is not None:
+            self._sync_sizes()
+        else:
+            n, src, dst = device_coo
+            self._n, self._m = int(n), int(src.numel())
+            self._dev_coo = (src, dst)
+
+    def _h(self):
+        if self._handle is None:
+            # the extraction validated the endpoints: straight into a new index
+            src, dst = (t.cpu() for t in self._dev_coo)
+            h = _call("_CAPI_DGLGraphCreateMutable", int(self._multigraph))
+            self._handle = h
+            _call("_CAPI_DGLGraphAddVertices", ("handle", h), self._n)
+            if self._m:
+                _call("_CAPI_DGLGraphAddEdges", ("handle", h), src, dst)
+        return ("handle", self._handle)
+
+    @property
+    def has_native_index(self):
+        """Whether the library's graph object exists yet. False for a subgraph
+        extracted on the device until a structural query (``edges()``,
+        degrees, ``in_edges`` ...) asks for it; message passing over the whole
+        subgraph on that device never does. Read-only."""
+        return self._handle is not None
+
+    @property
+    def induced_nodes(self):
+        """int64 parent id of every subgraph node (on the device for a device
+        extraction)."""
+        return self._induced_nodes
+
+    @property
+    def induced_edges(self):
+        """int64 parent id of every subgraph edge."""
+        return self._induced_edges
+
+    def _on_coo_device(self, ctx):
+        if self._dev_coo is None or ctx.type != "cuda":
+            return False
+        idx = ctx.index if ctx.index is not None else torch.cuda.current_device()
+        return self._dev_coo[0].device == torch.device("cuda", idx)
+
+    def adjacency(self, ctx):
+        ctx = torch.device(ctx)
+        if not self._on_coo_device(ctx):
+            return super(SubgraphIndex, self).adjacency(ctx)
+        ctx = self._dev_coo[0].device
+        key = ("adj", str(ctx))
+        if key not in self._cache:
+            src, dst = self._dev_coo
+            self._cache[key] = kernel.from_coo(self._n, self._n, dst, src, kernel.ORDER_EID, ctx,
+                                               validate=False)
+        return self._cache[key]
+
+    def incidence_in(self, ctx):
+        ctx = torch.device(ctx)
+        if not self._on_coo_device(ctx):
+            return super(SubgraphIndex, self).incidence_in(ctx)
+        key = ("inc_in", str(ctx))
+        if key not in self._cache:
+            dst = self._dev_coo[1]
+            eids = torch.arange(self._m, dtype=torch.int64, device=dst.device)
+            self._cache[key] = kernel.from_coo(self._n, self._m, dst, eids, kernel.ORDER_EID,
+                                               dst.device, validate=False)
+        return self._cache[key]
+
+    def add_nodes(self, num):
+        raise DGLError("Readonly graph. Mutation is not allowed.")
+
+    def add_edges(self, u, v):
+        raise DGLError("Readonly graph. Mutation is not allowed.")
+
+    def clear(self):
+        raise DGLError("Readonly graph. Mutation is not allowed.")
+
+    def __getstate__(self):
+        raise NotImplementedError("SubgraphIndex pickling is not supported yet.")
+
+    def __setstate__(self, state):
+        raise NotImplementedError("SubgraphIndex unpickling is not supported yet.")
+
+
+def map_to_subgraph_nid(subgraph_index, parent_nids):
+    """Subgraph ids of the parent node ids ``parent_nids`` (graph_index.py:
+    871-890, ``_CAPI_DGLMapSubgraphNID``); every id must be in the subgraph.
+    int64, host."""
+    return _call("_CAPI_DGLMapSubgraphNID", _as_i64(subgraph_index.induced_nodes),
+                 _as_i64(parent_nids))
 
 
 def _from_edges(n, src, dst, multigraph, readonly):
@@ -296,7 +448,7 @@ def disjoint_union(graphs):
     offset by the running sizes (graph_index.py:895-917): one
     ``_CAPI_DGLDisjointUnion`` call over the list of handles."""
     graphs = list(graphs)
-    handles = (ctypes.c_void_p * max(len(graphs), 1))(*[g._handle for g in graphs])
+    handles = (ctypes.c_void_p * max(len(graphs), 1))(*[g._h()[1] for g in graphs])
     h = _call("_CAPI_DGLDisjointUnion", ("handle", ctypes.addressof(handles)), len(graphs))
     return GraphIndex(any(g.is_multigraph() for g in graphs), False, handle=h)
 

@@ -2722,3 +2722,71 @@ def segment_reduce(x, offsets, reduce, weight=None):
     if x.dim() == 2:
         return _SegmentReduce.apply(x, w, segs, red)
     return _SegmentReduce.apply(x.reshape(N, F), w, segs, red).view((B,) + fshape)
+
+
+# ---------------------------------------------------------------------------
+# Node-induced subgraph on the device (csrc/induced_subgraph.hip)
+# ---------------------------------------------------------------------------
+SUBGRAPH_CHUNK = 512  # DGLHIP_SUBGRAPH_CHUNK: slots per item of the subgraph walk
+
+
+def induced_subgraph_count(csr, sel):
+    """Stage A of :func:`induced_subgraph` over the source-major ``csr`` and
+    the int64 device ids ``sel``: (workspace, [edges, invalid ids, duplicate
+    positions, items]), the four counts read once through pinned memory."""
+    dev = csr.device
+    N, n, nnz = csr.num_rows, sel.numel(), csr.nnz
+    nbytes = LIB.dglhip_induced_subgraph_workspace_bytes(N, n, nnz)
+    if nbytes < 0:
+        check_call(-1)
+    ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
+    status = torch.empty(4, dtype=torch.int64, device=dev)
+    check_call(LIB.dglhip_induced_subgraph_count_device(
+        N, n, nnz, ptr(csr.indptr), ptr(csr.indices) if nnz else None, ptr(sel) if n else None,
+        ptr(ws), int(nbytes), ptr(status), _stream_of(dev)))
+    host = torch.empty(4, dtype=torch.int64, pin_memory=True)
+    host.copy_(status, non_blocking=True)
+    torch.cuda.current_stream(dev).synchronize()
+    return ws, host.tolist()
+
+
+def induced_subgraph_fill(csr, sel, ws, items, m):
+    """Stage B: (src', dst', parent_eid), int64[m] each, on the device."""
+    dev = csr.device
+    out = torch.empty(3, m, dtype=torch.int64, device=dev)
+    if m:
+        check_call(LIB.dglhip_induced_subgraph_fill_device(
+            csr.num_rows, sel.numel(), csr.nnz, ptr(csr.indptr), ptr(csr.indices), ptr(csr.eid),
+            ptr(sel), ptr(ws), ws.numel(), int(items), int(m), ptr(out[0]), ptr(out[1]),
+            ptr(out[2]), _stream_of(dev)))
+    return out[0], out[1], out[2]
+
+
+def induced_subgraph(csr, sel):
+    """The subgraph of a graph induced by the nodes ``sel`` (int64, on the
+    device of ``csr``), from the graph's source-major CSR in edge-id order
+    (``SparseAdj.bwd`` of an ORDER_EID adjacency): ``(src', dst', parent_eid)``
+    with subgraph node ``i`` = ``sel[i]`` and the edges in the order of the
+    native index's vertex_subgraph (the out-edges of ``sel[0]``, ``sel[1]``,
+    ... in edge-id order that end inside the set).
+
+    One host read per call (the edge count and the validation counters), so
+    it cannot run while the current stream is being captured. An id outside
+    the graph or listed twice raises DGLError."""
+    dev = csr.device
+    if dev.type != "cuda":
+        raise DGLError("the device route of subgraph() needs a CSR on a ROCm device")
+    if torch.cuda.is_current_stream_capturing():
+        raise DGLError("subgraph() of device ids reads the subgraph's size on the host: "
+                       "it cannot run while a stream is being captured")
+    if sel.dtype.is_floating_point or sel.dtype == torch.bool:
+        raise DGLError("Index data must be an integer tensor, got %s" % sel.dtype)
+    sel = sel.detach().to(device=dev, dtype=torch.int64).reshape(-1).contiguous()
+    ws, (m, invalid, dup, items) = induced_subgraph_count(csr, sel)
+    if invalid:
+        raise DGLError("Invalid vertex: %d of the %d ids are not in a graph of %d nodes"
+                       % (invalid, sel.numel(), csr.num_rows))
+    if dup:
+        raise DGLError("subgraph() of device ids needs distinct nodes: %d of the %d ids repeat "
+                       "an earlier one" % (dup, sel.numel()))
+    return induced_subgraph_fill(csr, sel, ws, items, m)

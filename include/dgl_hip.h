@@ -482,6 +482,50 @@ int dglhip_segment_reduce_bwd_host(int reduce_op, int64_t num_segments, int64_t 
                                    float* dx, float* dw, int num_threads);
 
 /* ------------------------------------------------------------------------ */
+/* Node-induced subgraph on the device (csrc/induced_subgraph.hip): the      */
+/* reference's Graph::VertexSubgraph (src/graph/graph.cc:441-469) over a     */
+/* source-major CSR that is already on the device: indptr int64[num_nodes +  */
+/* 1], indices int32[nnz] (the destinations), eid int64[nnz]; row u holds    */
+/* the out-edges of u in edge-id order (DGLHIP_ORDER_EID).                   */
+/* selected: int64[num_selected] parent ids; subgraph node i is selected[i]. */
+/* For i = 0..num_selected-1 the out-edges of selected[i] in slot order      */
+/* whose destination is selected are emitted as (sub_src = i, sub_dst = the  */
+/* destination's position in `selected`, parent_eid = the slot's eid); the   */
+/* k-th emitted edge is subgraph edge k: the arrays of the native index's    */
+/* vertex_subgraph, element for element, the same on every run (positions    */
+/* come from two scans and wave ballots, not from atomics).                  */
+/* Two calls share one workspace, with one host read of `status` between     */
+/* them (so neither can run under stream capture):                           */
+/*   status[0] edges of the subgraph, status[1] ids outside [0, num_nodes),  */
+/*   status[2] positions whose id occurs more than once, status[3] items     */
+/*   (row chunks of at most DGLHIP_SUBGRAPH_CHUNK slots) the fill walks.     */
+/* An invalid id is counted and never used as an index; with status[1] or    */
+/* status[2] non-zero the other two entries mean nothing and the fill must   */
+/* not be called.                                                            */
+/* ------------------------------------------------------------------------ */
+#define DGLHIP_SUBGRAPH_CHUNK 512
+/* Bytes of the workspace the two calls share (-1 on an error): the          */
+/* membership map int32[num_nodes], the item list and the scans' storage.    */
+int64_t dglhip_induced_subgraph_workspace_bytes(int64_t num_nodes, int64_t num_selected,
+                                                int64_t nnz);
+/* Stage A: membership map, validation, item list, survivors per item and
+ * their scan; fills status (int64[4], device memory). No host sync inside. */
+int dglhip_induced_subgraph_count_device(int64_t num_nodes, int64_t num_selected, int64_t nnz,
+                                         const int64_t* indptr, const int32_t* indices,
+                                         const int64_t* selected, void* workspace,
+                                         int64_t workspace_bytes, int64_t* status,
+                                         void* stream);
+/* Stage B: writes the num_edges = status[0] entries of sub_src, sub_dst and
+ * parent_eid (int64 each) from the workspace stage A left, walking the
+ * num_items = status[3] items. Same sizes, CSR and `selected` as stage A. */
+int dglhip_induced_subgraph_fill_device(int64_t num_nodes, int64_t num_selected, int64_t nnz,
+                                        const int64_t* indptr, const int32_t* indices,
+                                        const int64_t* eid, const int64_t* selected,
+                                        void* workspace, int64_t workspace_bytes,
+                                        int64_t num_items, int64_t num_edges, int64_t* sub_src,
+                                        int64_t* sub_dst, int64_t* parent_eid, void* stream);
+
+/* ------------------------------------------------------------------------ */
 /* Weighted softmax cross-entropy over node rows (csrc/node_loss.hip): the   */
 /* loss of a full-graph node classifier. No reference counterpart: the       */
 /* reference's examples call torch's F.cross_entropy / nll_loss             */
