@@ -133,6 +133,7 @@ NDArray NDArray::Empty(const std::vector<int64_t>& shape, int code, int bits,
 
 NDArray NDArray::FromIds(const int64_t* p, int64_t n) {
   NDArray a = Ids(n);
+  if (n <= 0) return a;  // an empty vector's data() may be null: nothing to copy
   int64_t* dst = a.data<int64_t>();
   // threads share the first-touch page faults of the new buffer (10^9-id
   // exports of the graph index)
@@ -381,6 +382,7 @@ Registry& registry() {
     register_kernel_functions();
     register_graph_index_functions();
     register_scheduler_functions();
+    register_traversal_functions();
   });
   return raw_registry();
 }

@@ -166,5 +166,6 @@ void* current_stream(int device_id);
 void register_kernel_functions();
 void register_graph_index_functions();
 void register_scheduler_functions();
+void register_traversal_functions();
 
 }  // namespace dglhip

@@ -225,6 +225,14 @@ def _load():
                                                           _vp, _c_i64, _vp, _vp]),
         "dglhip_induced_subgraph_fill_device": (_c_int, [_c_i64, _c_i64, _c_i64] + [_vp] * 5 +
                                                 [_c_i64, _c_i64, _c_i64] + [_vp] * 4),
+        "dglhip_traversal_level_workspace_bytes": (_c_i64, [_c_i64, _c_i64]),
+        "dglhip_topological_init_workspace_bytes": (_c_i64, [_c_i64]),
+        "dglhip_bfs_init_device": (_c_int, [_c_i64, _c_i64, _vp, _vp, _c_i64, _vp, _vp, _vp, _vp]),
+        "dglhip_topological_init_device": (_c_int, [_c_i64, _c_i64] + [_vp] * 6 + [_c_i64, _vp,
+                                                                                   _vp]),
+        "dglhip_traversal_level_device": (_c_int, [_c_int, _c_i64, _c_i64] + [_vp] * 4 +
+                                          [_c_i64] * 3 + [_vp] * 5 + [_c_i64, _vp, _c_i64, _vp,
+                                                                      _vp]),
         "dglhip_xent_workspace_floats": (_c_int, []),
         "dglhip_xent_fwd_device": (_c_int, [_c_i64, _c_i64, _vp, _c_i64, _vp, _vp, _vp, _vp, _vp]),
         "dglhip_xent_bwd_device": (_c_int, [_c_i64, _c_i64, _vp, _c_i64, _vp, _vp, _vp, _vp,

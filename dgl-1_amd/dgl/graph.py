@@ -409,6 +409,41 @@ class DGLGraph(object):
         assert rf is not None
         scheduler.schedule_update_all(self, mf, rf, af)
 
+    def prop_nodes(self, nodes_generator, message_func="default", reduce_func="default",
+                   apply_node_func="default"):
+        """:meth:`pull` on each node frontier of ``nodes_generator`` in turn
+        (graph.py:2443-2517): an iterable of lists or tensors of node ids, such
+        as :func:`dgl.bfs_nodes_generator` or
+        :func:`dgl.topological_nodes_generator` return.
+
+        >>> g = dgl.DGLGraph(); g.add_nodes(4)
+        >>> g.ndata['x'] = torch.tensor([[1.], [2.], [3.], [4.]])
+        >>> g.add_edges([0, 1, 1, 2], [1, 2, 3, 3])
+        >>> g.register_message_func(lambda edges: {'m': edges.src['x']})
+        >>> g.register_reduce_func(lambda nodes: {'x': nodes.mailbox['m'].sum(1)})
+        >>> g.prop_nodes([[1, 2], [3]])
+        >>> g.ndata['x'].flatten()
+        tensor([1., 1., 2., 3.])
+        """
+        for frontier in nodes_generator:
+            self.pull(frontier, message_func, reduce_func, apply_node_func)
+
+    def prop_edges(self, edges_generator, message_func="default", reduce_func="default",
+                   apply_node_func="default"):
+        """:meth:`send_and_recv` on each edge frontier of ``edges_generator``
+        in turn (graph.py:2519-2593): an iterable of edge specifications (edge
+        ids, or ``(u, v)`` pairs), such as :func:`dgl.bfs_edges_generator` or
+        :func:`dgl.dfs_labeled_edges_generator` return.
+
+        With the graph of :meth:`prop_nodes`:
+
+        >>> g.prop_edges([([0, 1], [1, 3]), ([1, 2], [2, 3])])
+        >>> g.ndata['x'].flatten()
+        tensor([1., 1., 1., 3.])
+        """
+        for frontier in edges_generator:
+            self.send_and_recv(frontier, message_func, reduce_func, apply_node_func)
+
     # -- sparse views ----------------------------------------------------------
     def _cached_view(self, key, build):
         # per (view, arguments, ctx); cleared by mutation and clear_cache(),

@@ -55,6 +55,14 @@ def _call(api, *args):
     return getattr(_CAPI, api)(*args)
 
 
+_TRAVERSAL_CAPI = _ffi.CAPINamespace("traversal")
+
+
+def _call_trv(api, *args):
+    """A traversal._CAPI_* call."""
+    return getattr(_TRAVERSAL_CAPI, api)(*args)
+
+
 class GraphIndex(object):
     """Directed (multi)graph with integer node ids 0..N-1 and edge ids 0..E-1,
     stored in the library's native index (mutable, or immutable when
@@ -302,6 +310,70 @@ class GraphIndex(object):
         src, dst, eid = kernel.induced_subgraph(adj.bwd, v)
         nid = v.detach().to(torch.int64).reshape(-1)
         return SubgraphIndex(self, nid, eid, device_coo=(nid.numel(), src, dst))
+
+    # -- traversals (python/dgl/traversal.py -> traversal._CAPI_*) --------------
+    # Each returns (ids, sections): the frontiers are consecutive runs of the
+    # int64 tensor ``ids`` whose lengths are the Python list ``sections``.
+    def bfs_nodes(self, source, reverse=False):
+        """Node frontiers of a breadth-first search from ``source``
+        (``_CAPI_DGLBFSNodes``); the first frontier is ``source`` as given."""
+        f = _call_trv("_CAPI_DGLBFSNodes", self._h(), _as_i64(source), int(bool(reverse)))
+        return f(0), f(1).tolist()
+
+    def bfs_edges(self, source, reverse=False):
+        """The ids of the edges that discovered each node of
+        :meth:`bfs_nodes`' frontiers after the first (``_CAPI_DGLBFSEdges``)."""
+        f = _call_trv("_CAPI_DGLBFSEdges", self._h(), _as_i64(source), int(bool(reverse)))
+        return f(0), f(1).tolist()
+
+    def topological_nodes(self, reverse=False):
+        """Node frontiers in topological order (``_CAPI_DGLTopologicalNodes``);
+        a graph with a loop raises."""
+        f = _call_trv("_CAPI_DGLTopologicalNodes", self._h(), int(bool(reverse)))
+        return f(0), f(1).tolist()
+
+    def dfs_labeled_edges(self, source, reverse=False, has_reverse_edge=False,
+                          has_nontree_edge=False, return_labels=True):
+        """Edge frontiers of one depth-first search per source, merged
+        position-wise (``_CAPI_DGLDFSLabeledEdges``): (ids, labels, sections),
+        with ``labels`` None unless asked for."""
+        f = _call_trv("_CAPI_DGLDFSLabeledEdges", self._h(), _as_i64(source), int(bool(reverse)),
+                      int(bool(has_reverse_edge)), int(bool(has_nontree_edge)),
+                      int(bool(return_labels)))
+        if return_labels:
+            return f(0), f(1), f(2).tolist()
+        return f(0), None, f(1).tolist()
+
+    def dfs_edges(self, source, reverse=False):
+        """FORWARD edges of :meth:`dfs_labeled_edges` (``_CAPI_DGLDFSEdges``)."""
+        f = _call_trv("_CAPI_DGLDFSEdges", self._h(), _as_i64(source), int(bool(reverse)))
+        return f(0), f(1).tolist()
+
+    def _walk_csrs(self, ctx, reverse):
+        """(the CSR a device traversal walks, the opposite one) of a mutable
+        index: slots in edge-id order, which is the native index's slot order."""
+        if self._readonly:
+            raise DGLError("the device route needs a mutable index")
+        if torch.cuda.is_current_stream_capturing():  # before anything is launched
+            raise DGLError("a traversal reads every frontier's size on the host: it cannot "
+                           "run while a stream is being captured")
+        adj = self.adjacency(ctx)
+        return (adj.fwd, adj.bwd) if reverse else (adj.bwd, adj.fwd)
+
+    def bfs_nodes_device(self, source, reverse=False):
+        """:meth:`bfs_nodes` of a mutable index for ``source`` on a ROCm device,
+        computed there over the cached adjacency (kernel.bfs_frontiers): the
+        same frontiers in the same order, ``ids`` on the device."""
+        return kernel.bfs_frontiers(self._walk_csrs(source.device, reverse)[0], source)
+
+    def bfs_edges_device(self, source, reverse=False):
+        """:meth:`bfs_edges` on the device of ``source``."""
+        return kernel.bfs_frontiers(self._walk_csrs(source.device, reverse)[0], source,
+                                    edges=True)
+
+    def topological_nodes_device(self, ctx, reverse=False):
+        """:meth:`topological_nodes` computed on the ROCm device ``ctx``."""
+        return kernel.topological_frontiers(*self._walk_csrs(ctx, reverse))
 
     # -- pickling (graph_index.py:35-59): rebuildable from (n, multigraph, readonly, src, dst)
     def __getstate__(self):

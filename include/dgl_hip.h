@@ -526,6 +526,73 @@ int dglhip_induced_subgraph_fill_device(int64_t num_nodes, int64_t num_selected,
                                         int64_t* sub_dst, int64_t* parent_eid, void* stream);
 
 /* ------------------------------------------------------------------------ */
+/* BFS and topological frontiers on the device (csrc/traversal.hip): the     */
+/* reference's BFSNodes / BFSEdges / TopologicalNodes                        */
+/* (src/graph/traversal.h) over a CSR that is already on the device: indptr  */
+/* int64[num_nodes + 1], indices int32[nnz], eid int64[nnz]. Row u holds the */
+/* edges the walk follows out of u, in the native index's slot order: the    */
+/* source-major CSR forward, the destination-major one with `reverse`.       */
+/* The frontiers are those of the host queue loops (csrc/graph_traversal.cc),      */
+/* element for element and in the same order, the same on every run: the     */
+/* integer atomics only decide which slot discovers a node, positions come   */
+/* from scans and wave ballots.                                              */
+/* The caller owns the level loop. The queue is one int64 array: a level     */
+/* reads its frontier from it and writes the next frontier behind it. An     */
+/* init call, then one level call per frontier, each followed by one host    */
+/* read of `status` (int64[4], device memory), so none of the calls can run  */
+/* under stream capture:                                                     */
+/*   status[0] length of the next frontier (after an init call: the first),  */
+/*   status[1] its candidate total: the sum of its rows' degrees,            */
+/*   status[2] ids of the frontier just read that are outside [0, num_nodes) */
+/*             (after dglhip_bfs_init_device: of the sources); such an id is */
+/*             counted and never used as an index,                           */
+/*   status[3] items (row chunks of at most DGLHIP_TRAVERSAL_CHUNK slots)    */
+/*             the level walked; 0 after an init call.                       */
+/* The loop ends when status[0] is 0. State between the levels: claim        */
+/* uint64[num_nodes], and visited uint8[num_nodes] (BFS) or remain           */
+/* int64[num_nodes] (topological), initialised by the init call.             */
+/* ------------------------------------------------------------------------ */
+#define DGLHIP_TRAVERSAL_CHUNK 512
+#define DGLHIP_TRAVERSE_BFS 0
+#define DGLHIP_TRAVERSE_TOPOLOGICAL 1
+/* Bytes of one level's workspace for a frontier of frontier_len >= 1 rows    */
+/* holding num_candidates slots (-1 on an error).                            */
+int64_t dglhip_traversal_level_workspace_bytes(int64_t frontier_len, int64_t num_candidates);
+/* Bytes of dglhip_topological_init_device's workspace (-1 on an error). */
+int64_t dglhip_topological_init_workspace_bytes(int64_t num_nodes);
+/* BFS level zero: resets claim and visited and validates the sources. The
+ * first frontier is `source` itself (the caller copies it to the head of the
+ * queue, repeated ids included); status = {num_sources, candidate total of the
+ * in-range sources, ids out of range, 0}. */
+int dglhip_bfs_init_device(int64_t num_nodes, int64_t nnz, const int64_t* indptr,
+                           const int64_t* source, int64_t num_sources, uint64_t* claim,
+                           uint8_t* visited, int64_t* status, void* stream);
+/* Topological level zero: remain[v] = opposite_indptr[v + 1] -
+ * opposite_indptr[v] (v's degree in the other direction's CSR), claim reset,
+ * and the nodes with remain 0 written to out[0 .. status[0]) in ascending id
+ * (out has room for num_nodes ids). indptr is that of the CSR the levels walk:
+ * status[1] sums its degrees over the first frontier. */
+int dglhip_topological_init_device(int64_t num_nodes, int64_t nnz, const int64_t* indptr,
+                                   const int64_t* opposite_indptr, uint64_t* claim,
+                                   int64_t* remain, int64_t* out, void* workspace,
+                                   int64_t workspace_bytes, int64_t* status, void* stream);
+/* One level: frontier[0 .. frontier_len) in queue order to next[0 ..
+ * status[0]) in queue order. num_candidates is the status[1] the previous call
+ * left. key_base (topological; 0 for BFS) is 1 + the sum of num_candidates over
+ * the earlier levels. next has room for next_capacity ids and nothing is
+ * written past it; a status[0] above it is an error for the caller to raise.
+ * next_edge (or NULL; needs eid) receives the edge id that discovered each
+ * node of `next`. visited is used by DGLHIP_TRAVERSE_BFS, remain by
+ * DGLHIP_TRAVERSE_TOPOLOGICAL; the other may be NULL. */
+int dglhip_traversal_level_device(int mode, int64_t num_nodes, int64_t nnz, const int64_t* indptr,
+                                  const int32_t* indices, const int64_t* eid,
+                                  const int64_t* frontier, int64_t frontier_len,
+                                  int64_t num_candidates, int64_t key_base, uint64_t* claim,
+                                  uint8_t* visited, int64_t* remain, int64_t* next,
+                                  int64_t* next_edge, int64_t next_capacity, void* workspace,
+                                  int64_t workspace_bytes, int64_t* status, void* stream);
+
+/* ------------------------------------------------------------------------ */
 /* Weighted softmax cross-entropy over node rows (csrc/node_loss.hip): the   */
 /* loss of a full-graph node classifier. No reference counterpart: the       */
 /* reference's examples call torch's F.cross_entropy / nll_loss             */
