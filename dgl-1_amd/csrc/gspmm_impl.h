@@ -345,6 +345,116 @@ __global__ __launch_bounds__(256) void gspmm_sum_kernel(
   }
 }
 
+// Two items per wave: the blocked schedule's items for copy_u over fp32 rows
+// of 128 floats (DESIGN.md §4.1 "Two items per wave"). Wave w takes items 2w
+// (lanes 0-31) and 2w + 1 (lanes 32-63), each lane 4 consecutive floats, so
+// one gather instruction fetches two whole source rows (1 KiB) and a short
+// item's round trips carry twice the payload. Both items' column ids come
+// from the scalar slot stream; a lane picks its half's id and gathers at a
+// 32-bit byte offset from the table's one buffer descriptor (the launcher's
+// gate: the table is shorter than 4 GiB). Each lane adds its item's slots in
+// slot order from zero (ACCUM: from the running row): the chain of
+// gspmm_sum_kernel, so the same bits. Slots that only the longer item has run
+// with the shorter half's lanes switched off: nothing fetched, nothing added
+// (not even a zero: -0.0 + 0.0 is +0.0). An odd item count ends on a wave whose upper half is off. Running
+// rows as RP 2 (ACCUM) / RP 4 of the one-item kernel, 16 bytes per lane.
+template <int DEPTH, bool ACCUM>
+__global__ __launch_bounds__(256) void gspmm_items_pair_kernel(
+    int64_t num_items, int64_t ldu, uint32_t table_bytes,
+    const int32_t* __restrict__ indices, const float* __restrict__ ufeat,
+    float* __restrict__ out, const int32_t* __restrict__ item_rows,
+    const int64_t* __restrict__ item_ptr) {
+  typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+  constexpr int64_t F = 128;
+  const int lane = threadIdx.x & 63;
+  const int64_t wave =
+      block_linear() * (blockDim.x >> 6) +
+      __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
+  const int64_t i0 = wave * 2;
+  if (i0 >= num_items) return;
+  const bool two = i0 + 1 < num_items;  // uniform
+  const bool hi = lane >= 32;
+  // slots [b0, b1) into row r0, [b1, e1) into row r1
+  const int64_t b0 = item_ptr[i0], b1 = item_ptr[i0 + 1];
+  const int64_t e1 = two ? item_ptr[i0 + 2] : b1;
+  const int64_t r0 = item_rows[i0];
+  const int64_t r1 = two ? item_rows[i0 + 1] : r0;
+  const int n0 = static_cast<int>(b1 - b0), n1 = static_cast<int>(e1 - b1);
+  const int nmin = n0 < n1 ? n0 : n1, nmax = n0 < n1 ? n1 : n0;
+  const int32_t* __restrict__ idx0 = indices + b0;
+  const int32_t* __restrict__ idx1 = indices + b1;
+  const uint32_t ld4 = static_cast<uint32_t>(ldu) * 4u;
+  const uint32_t lane_off = static_cast<uint32_t>(lane & 31) * 16u;
+  const __amdgpu_buffer_rsrc_t table = __builtin_amdgcn_make_buffer_rsrc(
+      const_cast<float*>(ufeat), 0, static_cast<int>(table_bytes), 0x00020000);
+  const int64_t f0 = int64_t(lane & 31) * 4;
+  float* const orow = out + (hi ? r1 : r0) * F;
+  const bool owns = !hi || two;
+
+  f32x4 acc = Vec<4>::zero();
+  if (ACCUM && owns) acc = load_out<4, 2>(orow, f0);
+  int k = 0;
+  // both items have DEPTH slots left: every lane gathers, no predicate
+#pragma unroll 1
+  for (; k + DEPTH <= nmin; k += DEPTH) {
+    u32x4 v[DEPTH];
+#pragma unroll
+    for (int j = 0; j < DEPTH; ++j) {
+      const uint32_t o0 = static_cast<uint32_t>(idx0[k + j]) * ld4;
+      const uint32_t o1 = static_cast<uint32_t>(idx1[k + j]) * ld4;
+      v[j] = __builtin_amdgcn_raw_buffer_load_b128(table, (hi ? o1 : o0) + lane_off, 0, 0);
+    }
+#pragma unroll
+    for (int j = 0; j < DEPTH; ++j) acc += *reinterpret_cast<const f32x4*>(&v[j]);
+  }
+  // the rest as predicated batches, every gather of a batch in flight
+  // together. A lane whose item has no slot k + j is switched off for it: its
+  // gather goes to an offset past the table, which the descriptor's range
+  // check answers without a fetch, and the value is not added. The scalar
+  // column loads stay inside the pair's slots (an ended item re-reads its
+  // last id, an empty one the other item's).
+  const int my_n = hi ? n1 : n0;
+  const int32_t* __restrict__ tail0 = n0 > 0 ? idx0 : idx1;
+  const int32_t* __restrict__ tail1 = n1 > 0 ? idx1 : idx0;
+  const int last0 = n0 > 0 ? n0 - 1 : n1 - 1, last1 = n1 > 0 ? n1 - 1 : n0 - 1;
+#pragma unroll 1
+  for (; k < nmax; k += DEPTH) {
+    const int rb = nmax - k;
+    u32x4 v[DEPTH];
+    int32_t c0[DEPTH], c1[DEPTH];
+    // the batch's ids first, all in flight: one scalar round trip, not one
+    // ahead of every gather (the empty asm keeps the compiler from sinking
+    // each load to its use)
+#pragma unroll
+    for (int j = 0; j < DEPTH; ++j) {
+      c0[j] = tail0[k + j < last0 ? k + j : last0];
+      c1[j] = tail1[k + j < last1 ? k + j : last1];
+    }
+#pragma unroll
+    for (int j = 0; j < DEPTH; ++j) asm volatile("" : "+s"(c0[j]), "+s"(c1[j]));
+#pragma unroll
+    for (int j = 0; j < DEPTH; ++j) {
+      if (j < rb) {  // uniform
+        const uint32_t o0 = static_cast<uint32_t>(c0[j]) * ld4;
+        const uint32_t o1 = static_cast<uint32_t>(c1[j]) * ld4;
+        const uint32_t off = k + j < my_n ? (hi ? o1 : o0) + lane_off : 0xfffffff0u;
+        v[j] = __builtin_amdgcn_raw_buffer_load_b128(table, off, 0, 0);
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < DEPTH; ++j) {
+      if (j < rb) {
+        const f32x4 sum = acc + *reinterpret_cast<const f32x4*>(&v[j]);
+        acc = k + j < my_n ? sum : acc;
+      }
+    }
+  }
+  // one store per half: the row of a half is uniform, as store_out's
+  // descriptor has to be
+  if (!hi) store_out<4, ACCUM ? 2 : 4>(out + r0 * F, f0, acc);
+  else if (two) store_out<4, ACCUM ? 2 : 4>(out + r1 * F, f0, acc);
+}
+
 // Combine the chunk partials of each heavy row in chunk order:
 // out[row] = ((p0 + p1) + p2) + ... (deterministic), then MEAN scaling; with
 // ACCUM the row's running value comes first: out[row] = ((out[row] + p0) + p1) ...;
@@ -548,6 +658,8 @@ struct SumLaunch {
   bool accumulate;           // continue each item's chain from the value in `out`
   bool nt_out = false;       // non-temporal output stores (see stream_output)
   int64_t ldu = 0;           // ufeat row stride in elements (0: F)
+  int64_t urows = 0;         // rows of ufeat (0: not known)
+  int items_per_wave = 1;    // 2: gspmm_items_pair_kernel where it applies
 };
 
 // Outputs past twice the 256 MiB Infinity Cache are stored non-temporally
@@ -556,6 +668,34 @@ struct SumLaunch {
 // cache-policy study). Covers copy_u + sum at VEC 2 x 64 lanes.
 static inline bool stream_output(int64_t rows, int64_t feat_len) {
   return rows * feat_len * int64_t(sizeof(float)) > (int64_t(512) << 20);
+}
+
+// Whether a copy_u launch of the blocked schedule's items takes the two-
+// items-per-wave kernel: fp32 rows of 128 floats, 16-byte lanes (the table,
+// its row stride and out aligned to them) and 32-bit gather offsets (the
+// table shorter than 4 GiB, which needs its row count).
+static inline bool items_pair_applies(const SumLaunch& a) {
+  const int64_t ldu = a.ldu ? a.ldu : a.F;
+  return a.items_per_wave == 2 && a.F == 128 && a.urows > 0 && ldu % 4 == 0 &&
+         reinterpret_cast<uintptr_t>(a.ufeat) % 16 == 0 &&
+         reinterpret_cast<uintptr_t>(a.out) % 16 == 0 &&
+         a.urows * ldu * int64_t(sizeof(float)) < (int64_t(1) << 32);
+}
+
+static inline void launch_items_pair(const SumLaunch& a, hipStream_t stream) {
+  // 10 pairs of rows in flight per wave: the most that keep 64 VGPRs, so 8
+  // waves per SIMD (8 / 10 / 12 / 16 measured: DESIGN.md §4.1 "Two items per wave")
+  constexpr int DEPTH = 10;
+  const int64_t blocks = (a.num_items + 7) / 8;  // 4 waves of 2 items
+  DGLHIP_CHECK(blocks <= 0x7fffffff, "grid too large: " << blocks);
+  const int64_t ldu = a.ldu ? a.ldu : a.F;
+  auto kernel = a.accumulate ? gspmm_items_pair_kernel<DEPTH, true>
+                             : gspmm_items_pair_kernel<DEPTH, false>;
+  timed_launch(stream, [&] {
+    hipLaunchKernelGGL(kernel, grid_1d(blocks), dim3(256), 0, stream, a.num_items, ldu,
+                       static_cast<uint32_t>(a.urows * ldu * int64_t(sizeof(float))), a.indices,
+                       a.ufeat, a.out, a.row_order, a.chunk_beg);
+  });
 }
 
 template <int VEC, int GROUP, int MSG, int EM, bool MEAN>
@@ -588,6 +728,11 @@ static inline void launch_sum(const SumLaunch& a, hipStream_t stream) {
       // offset for all 16: 42 instead of 70 VGPRs, 8 waves per SIMD instead of
       // 7; Reddit-shaped headline 3.74 -> 3.61 ms, same bits); the running
       // rows under RP 2, the first launch, which only stores, under RP 4.
+      // With items_per_wave 2, rows of 128 floats go two items to a wave.
+      if (items_pair_applies(a)) {
+        launch_items_pair(a, stream);
+        return;
+      }
       if (a.accumulate)
         kernel = gspmm_sum_kernel<VEC, GROUP, UNROLL, MSG, EM, false, true, true, POL_DEFAULT,
                                   true, 2>;

@@ -53,6 +53,7 @@ SpmmPolicy policy_from_env() {
   p.block_max_stretch = std::stod(env_str("DGLHIP_BLOCK_MAX_STRETCH", "3"));
   p.short_rows = env_str("DGLHIP_SHORT_ROWS", "on") != "off";
   p.pad_rows = env_str("DGLHIP_PAD_ROWS", "auto") == "auto";
+  p.items_per_wave = env_str("DGLHIP_ITEMS_PER_WAVE", "2") == "1" ? 1 : 2;
   return p;
 }
 
@@ -126,6 +127,8 @@ void set_spmm_policy(const SpmmPolicy& p) {
                    p.block_max_suffix >= 0 && p.tier_min_rows >= 0 && p.pad_min_bytes >= 0,
                "invalid g-SpMM schedule policy");
   DGLHIP_CHECK(p.row_split >= -1, "row_split: -1 auto, 0 off or a chunk length");
+  DGLHIP_CHECK(p.items_per_wave == 1 || p.items_per_wave == 2,
+               "items_per_wave " << p.items_per_wave << ": 1 or 2");
   std::lock_guard<std::mutex> lk(g_pol_mu);
   pol_ref() = p;
 }
@@ -828,6 +831,7 @@ struct Decision {
   // mean_add on the blocked schedule: the running sums' own rows (out holds
   // the value the mean is added to)
   int64_t ws_sums = 0;
+  int items_per_wave = 1;  // blocked items a wave takes (gspmm_items_pair_kernel: 2)
   int64_t total() const { return ws_pad + ws_vals + ws_map + ws_partial + ws_sums; }
 };
 
@@ -901,6 +905,15 @@ Decision decide(SpmmPlan& plan, const RunArgs& a, hipStream_t s) {
     d.bp = plan.blocked(ld_in * elem, p.block_bytes, s);
     if (d.bp) {
       d.path = PATH_BLOCKED;
+      // Two items per wave where the slices are L2-sized. Slices the slot
+      // rule stretched past 1.5 x block_bytes are gathered from the Infinity
+      // Cache, and there the pair kernel's second dependent batch (items of
+      // 12-13 slots against 10 in flight) costs more than its 16-byte
+      // gathers save: the emulated N = 4 rank's 12-MB slices ran 6.50 ms
+      // against the one-item kernel's 6.34.
+      const auto lh = plan.span(s);
+      const double slice = static_cast<double>(lh.second - lh.first) * ld_in * elem / d.bp->B;
+      d.items_per_wave = p.items_per_wave == 2 && slice <= 1.5 * p.block_bytes ? 2 : 1;
       if (mean_add) d.ws_sums = align256(plan.num_rows() * a.F * 4);
       if (!strided && fp32u && pad_rows(p, a.msg, DGLHIP_REDUCE_SUM, a.F, a.urows)) {
         d.pad = true;
@@ -1048,10 +1061,11 @@ void run_planned(SpmmPlan& plan, const RunArgs& a, const Decision& d, void* work
     }
     for (size_t i = 0; i < bp.launches.size(); ++i) {
       const BlockItems& it = bp.launches[i];
-      DGLHIP_CHECK(dglhip_gspmm_items_device(
+      DGLHIP_CHECK(dglhip_gspmm_items_table_device(
                        a.msg, it.n_items, a.F, it.rows.data<int32_t>(), it.ptr.data<int64_t>(),
                        (i == 0 && first_writes) ? 0 : 1, bp.indices.data<int32_t>(),
-                       ev ? nullptr : erows, static_cast<const float*>(uf), d.ld,
+                       ev ? nullptr : erows, static_cast<const float*>(uf), d.ld, a.urows,
+                       d.items_per_wave,
                        ev ? ev : (a.msg == DGLHIP_MSG_U_MUL_E ? a.efeat : nullptr),
                        elen, sums, s) == 0,
                    DGLGetLastError());
@@ -1241,6 +1255,7 @@ int dglhip_spmm_get_policy(DGLHipSpmmPolicy* out) {
   out->blocked = p.blocked;
   out->short_rows = p.short_rows;
   out->pad_rows = p.pad_rows;
+  out->items_per_wave = p.items_per_wave;
   out->block_bytes = p.block_bytes;
   out->block_table_min = p.block_table_min;
   out->block_table_max = p.block_table_max;
@@ -1261,6 +1276,7 @@ int dglhip_spmm_set_policy(const DGLHipSpmmPolicy* in) {
   p.blocked = in->blocked != 0;
   p.short_rows = in->short_rows != 0;
   p.pad_rows = in->pad_rows != 0;
+  p.items_per_wave = in->items_per_wave;
   p.block_bytes = in->block_bytes;
   p.block_table_min = in->block_table_min;
   p.block_table_max = in->block_table_max;

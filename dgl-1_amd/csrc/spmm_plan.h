@@ -42,6 +42,7 @@ struct SpmmPolicy {
   int blocked = 1;                 // source-blocked schedule where exact (0: off)
   int short_rows = 1;              // short-row tiers (0: off)
   int pad_rows = 1;                // padded-stride gathers (0: off)
+  int items_per_wave = 2;          // blocked items per wave (gspmm_items_pair_kernel), or 1
   int64_t block_bytes = 6 << 20;   // source slice per launch
   int64_t block_table_min = 16 << 20;
   int64_t block_table_max = 256 << 20;

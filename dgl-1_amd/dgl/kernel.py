@@ -94,14 +94,14 @@ _WAVES = {}
 class _Policy(ctypes.Structure):
     _fields_ = [("row_split", ctypes.c_int64), ("blocked", ctypes.c_int32),
                 ("short_rows", ctypes.c_int32), ("pad_rows", ctypes.c_int32),
-                ("reserved", ctypes.c_int32), ("block_bytes", ctypes.c_int64),
+                ("items_per_wave", ctypes.c_int32), ("block_bytes", ctypes.c_int64),
                 ("block_table_min", ctypes.c_int64), ("block_table_max", ctypes.c_int64),
                 ("block_min_slots", ctypes.c_int64), ("block_max_stretch", ctypes.c_double),
                 ("block_max_suffix", ctypes.c_double), ("block_min_row_bytes", ctypes.c_int64),
                 ("tier_min_rows", ctypes.c_int64), ("pad_min_bytes", ctypes.c_int64)]
 
 
-_POLICY_KEYS = tuple(n for n, _ in _Policy._fields_ if n != "reserved")
+_POLICY_KEYS = tuple(n for n, _ in _Policy._fields_)
 # bumped at every policy change: part of the keys of the Python-side caches
 # of native plan structures (a new policy may give a CSR another schedule)
 _POLICY_GEN = [0]
@@ -109,7 +109,8 @@ _POLICY_GEN = [0]
 
 def schedule_policy():
     """The g-SpMM schedule policy as a dict (row_split -1 auto / 0 off / a
-    chunk length, blocked, short_rows, pad_rows, block_bytes, block_table_min,
+    chunk length, blocked, short_rows, pad_rows, items_per_wave (1 or 2: the
+    blocked schedule's items a wave takes), block_bytes, block_table_min,
     block_table_max, block_min_slots, block_max_stretch, block_max_suffix,
     block_min_row_bytes, tier_min_rows, pad_min_bytes)."""
     p = _Policy()

@@ -261,11 +261,12 @@ typedef struct DGLHipSpmmPlanObj* DGLHipSpmmPlan;
 
 /* Schedule policy (process-wide). Defaults: row_split -1 (auto: chunk a row
  * only when it is the launch's critical path), blocked 1, short_rows 1,
- * pad_rows 1, block_bytes 6 MiB, block_table_min 16 MiB, block_table_max
+ * pad_rows 1, items_per_wave 2, block_bytes 6 MiB, block_table_min 16 MiB, block_table_max
  * 256 MiB, block_min_slots 12, block_max_stretch 3, block_max_suffix 1/16,
  * block_min_row_bytes 128, tier_min_rows 65536, pad_min_bytes 4 MiB; the
  * environment variables DGLHIP_ROW_SPLIT / _BLOCKED / _BLOCK_BYTES /
- * _BLOCK_MIN_SLOTS / _BLOCK_MAX_STRETCH / _SHORT_ROWS / _PAD_ROWS set the
+ * _BLOCK_MIN_SLOTS / _BLOCK_MAX_STRETCH / _SHORT_ROWS / _PAD_ROWS /
+ * _ITEMS_PER_WAVE set the
  * initial values. Results never depend on it beyond the documented
  * tolerance of the heavy-row split (re-association of a chunked row). */
 typedef struct {
@@ -273,7 +274,7 @@ typedef struct {
   int32_t blocked;        /* source-blocked schedule where exact */
   int32_t short_rows;     /* short-row tiers */
   int32_t pad_rows;       /* padded-stride gathers of line-straddling rows */
-  int32_t reserved;
+  int32_t items_per_wave; /* blocked items per wave: 2 where the pair kernel applies, or 1 */
   int64_t block_bytes;    /* source slice per launch */
   int64_t block_table_min, block_table_max;  /* gathered table range that blocks */
   int64_t block_min_slots;                   /* slots per row and block */
@@ -752,6 +753,17 @@ int dglhip_gspmm_items_device(int msg_op, int64_t num_items, int64_t feat_len,
                               const int32_t* indices, const int64_t* eid, const float* ufeat,
                               int64_t ufeat_ld, const float* efeat, int64_t efeat_len,
                               float* out, void* stream);
+/* The same with the row count of ufeat given (0: not known) and the items a
+ * wave takes: 1, or 2 (the schedule policy's items_per_wave), which runs
+ * copy_u over fp32 rows of 128 floats two items to a wave, 16 bytes per lane,
+ * where ufeat, out and the row stride are 16-byte aligned and ufeat is
+ * shorter than 4 GiB, and as 1 everywhere else. The same bits either way. */
+int dglhip_gspmm_items_table_device(int msg_op, int64_t num_items, int64_t feat_len,
+                                    const int32_t* item_rows, const int64_t* item_ptr,
+                                    int accumulate, const int32_t* indices, const int64_t* eid,
+                                    const float* ufeat, int64_t ufeat_ld, int64_t ufeat_rows,
+                                    int items_per_wave, const float* efeat, int64_t efeat_len,
+                                    float* out, void* stream);
 
 /* Source-swept copy_u + sum (mean != 0: mean) of fp32 rows of feat_len = 64,
  * 128 or 256 floats over the CSR (indptr, indices), every row of out

@@ -2,9 +2,12 @@
 (kernel.timing_enable(per_call=True): two events per call, none between the
 launches), on the Reddit-shaped graph (copy_u + sum, F = 128): the earlier
 sweeps bracketed every launch, which charged schedules with more launches
-for their markers. Bits compared with the one-launch kernel.
+for their markers. Bits compared with the one-launch kernel. With several
+--items-per-wave values each slice runs under each of them (1: the one-item
+kernel, 2: gspmm_items_pair_kernel), interleaved in every round.
 
   python tools/block_bytes_percall.py [--mib 3 4 5 6 8] [--rounds 3] [--iters 20]
+      [--items-per-wave 1 2]
 """
 import argparse
 import json
@@ -23,6 +26,8 @@ def main():
     ap.add_argument("--mib", type=float, nargs="+", default=[3, 4, 5, 6, 8])
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--items-per-wave", type=int, nargs="+", default=None,
+                    help="policy values to run each slice under (default: the current one)")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     src, dst, n = data.reddit_like(device=dev)
@@ -35,21 +40,24 @@ def main():
     kernel.gspmm_into(csr, out, h)
     ref = out.clone()
     kernel.set_blocked(old)
+    ipws = args.items_per_wave or [kernel.schedule_policy()["items_per_wave"]]
     res = {"graph": "reddit_like", "rounds": []}
     for _ in range(args.rounds):
         row = {}
         for mib in args.mib:
-            kernel.set_schedule_policy(block_bytes=int(mib * (1 << 20)))
-            kernel.gspmm_into(csr, out, h)
-            torch.cuda.synchronize()
-            same = bool(torch.equal(out, ref))
-            kernel.timing_enable(True, per_call=True)
-            for _ in range(args.iters):
+            for ipw in ipws:
+                kernel.set_schedule_policy(block_bytes=int(mib * (1 << 20)), items_per_wave=ipw)
                 kernel.gspmm_into(csr, out, h)
-            ms, calls = kernel.timing_read()
-            kernel.timing_enable(False)
-            row["%g" % mib] = {"ms": ms / calls, "blocks": kernel.blocked_schedule(adj, h),
-                               "bits_equal": same}
+                torch.cuda.synchronize()
+                same = bool(torch.equal(out, ref))
+                kernel.timing_enable(True, per_call=True)
+                for _ in range(args.iters):
+                    kernel.gspmm_into(csr, out, h)
+                ms, calls = kernel.timing_read()
+                kernel.timing_enable(False)
+                key = "%g" % mib if args.items_per_wave is None else "%g/ipw%d" % (mib, ipw)
+                row[key] = {"ms": ms / calls, "blocks": kernel.blocked_schedule(adj, h),
+                            "bits_equal": same}
         res["rounds"].append(row)
         print(json.dumps(row), flush=True)
     print(json.dumps(res))
