@@ -1,0 +1,462 @@
+// Uniform neighbour sampling of a graph whose CSR is on the device: the device
+// route of dgl.contrib.sampling.NeighborSampler for seeds given as a device
+// tensor.
+//
+// The answer is that of the native index's sample_neighbors (graph_index.cc;
+// the reference's ImmutableGraph::SampleSubgraph + CompactSubgraph) with the
+// draw replaced by the stateless rule of sample_key.h: a row of d slots at
+// fan-out k keeps every slot when d <= k, else the k positions with the
+// smallest (key(seed, v, p), p), in ascending p. Seeds are layer 0 (a repeated
+// seed counts once); a vertex first reached while layer h is expanded gets
+// layer h + 1; vertices of layer < num_hops are expanded, each once. The
+// subgraph's vertices are the visited ids ascending; its edges are the selected
+// slots of the expanded vertices in ascending id, each row in ascending
+// position. Everything is a function of (CSR, seeds, num_hops, k, seed): the
+// host twin (neighbor_sample_host.cc) gives the same arrays bit for bit.
+//
+// Stages, the level loop being the caller's with one host read of `status`
+// after the init call and after every hop:
+//   init  layer[N] = -1; a seed in [0, N) claims layer 0 with a compare-and-
+//         swap and the winners form frontier 0; the others are counted and
+//         never used as an index.
+//   hop h one wave per frontier vertex, four per 256-lane workgroup. The wave
+//         computes its row's selection and claims every selected neighbour
+//         with atomicCAS(&layer[nbr], -1, h + 1); the winners of a stride are
+//         appended to the next frontier with one atomicAdd per wave. The order
+//         of a frontier is arbitrary and nothing in the output depends on it;
+//         the layers do not depend on who wins because hop h is complete
+//         before hop h + 1 starts. The rows' min(d, k) are summed into the
+//         status, so after the last hop the caller knows the vertex and the
+//         edge count and the final stage needs no read.
+//   final one scan over layer >= 0 gives every visited vertex its subgraph id
+//         (vertices, layers); min(d, k) of the expanded ones is scanned into
+//         each row's output base; the fill launch recomputes each expanded
+//         row's selection and writes edge base + rank, rank from the ballots
+//         below the lane. No atomic decides a position.
+//
+// Selecting the k smallest of d keys in a wave: an MSB-first binary radix
+// select on the 64-bit key. Pass b counts the keys that agree with the prefix
+// found so far and have bit b clear; the k-th smallest has bit b clear exactly
+// when that count reaches the rank still wanted. After 64 passes the prefix is
+// the k-th smallest key T and the rank left over is how many keys equal to T
+// are taken, first positions first. Rows of at most DGLHIP_SAMPLE_REG_SLOTS
+// slots keep their keys in registers (DGLHIP_SAMPLE_REG_SLOTS / 64 per lane)
+// and count with ballots; longer rows recompute the hash in every pass and
+// reduce per-lane counts once per pass. The cost does not depend on k and no
+// row is too long. Only the selected slots' indices and eid are read: the key
+// depends on the position, not on the neighbour.
+#include "../../include/dgl_hip.h"
+#include "common.h"
+#include "launch.h"
+#include "sample_key.h"
+#include "timing.h"
+
+#include <hip/hip_runtime.h>
+#include <rocprim/device/device_scan.hpp>
+#include <rocprim/iterator/transform_iterator.hpp>
+
+namespace dglhip {
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kWaves = kThreads / 64;
+constexpr int kRegSlots = DGLHIP_SAMPLE_REG_SLOTS;
+constexpr int kRegKeys = kRegSlots / 64;
+
+static_assert(kRegSlots % 64 == 0 && kRegKeys >= 1 && kRegKeys <= 8,
+              "the register path holds a few whole strides of keys per lane");
+
+using u64 = unsigned long long;
+
+int64_t round256(int64_t v) { return (v + 255) & ~int64_t(255); }
+
+struct IsVisited {
+  __host__ __device__ int32_t operator()(int32_t layer) const { return layer >= 0 ? 1 : 0; }
+};
+
+using VisitedIter = rocprim::transform_iterator<const int32_t*, IsVisited, int32_t>;
+
+size_t scan_bytes_i64(int64_t len) {
+  size_t bytes = 0;
+  HIP_CALL(rocprim::inclusive_scan(nullptr, bytes, static_cast<const int64_t*>(nullptr),
+                                   static_cast<int64_t*>(nullptr), size_t(len),
+                                   rocprim::plus<int64_t>()));
+  return bytes;
+}
+
+size_t scan_bytes_visited(int64_t len) {
+  size_t bytes = 0;
+  HIP_CALL(rocprim::inclusive_scan(nullptr, bytes,
+                                   VisitedIter(static_cast<const int32_t*>(nullptr), IsVisited()),
+                                   static_cast<int32_t*>(nullptr), size_t(len),
+                                   rocprim::plus<int32_t>()));
+  return bytes;
+}
+
+// The workspace of the final stage (all sections 256-byte aligned).
+struct Layout {
+  int64_t pos, cnt, base, scan, scan_len, total;
+  Layout(int64_t N, int64_t V) {
+    int64_t o = 0;
+    pos = o; o += round256(N * 4);
+    cnt = o; o += round256(V * 8);
+    base = o; o += round256((V + 1) * 8);
+    scan = o;
+    const size_t s0 = N > 0 ? scan_bytes_visited(N) : 0, s1 = V > 0 ? scan_bytes_i64(V) : 0;
+    scan_len = round256(int64_t(s0 > s1 ? s0 : s1));
+    total = o + scan_len;
+  }
+};
+
+// Slots [*beg, *end) of row v (v in [0, N)), clamped to the index arrays.
+__device__ __forceinline__ void row_range(const int64_t* indptr, int64_t nnz, int64_t v,
+                                          int64_t* beg, int64_t* end) {
+  int64_t b = indptr[v], e = indptr[v + 1];
+  b = b < 0 ? 0 : (b > nnz ? nnz : b);
+  e = e < b ? b : (e > nnz ? nnz : e);
+  *beg = b;
+  *end = e;
+}
+
+// The sum of c over the wave, in every lane.
+__device__ __forceinline__ int64_t wave_sum(int64_t c) {
+  long long v = c;
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+
+// The k-th smallest (1-based, 1 <= k < d) of the d keys of a row in *thresh,
+// and how many of the keys equal to it are taken in *take_eq. Every lane of the
+// wave calls it with the same arguments and gets the same answer.
+__device__ __forceinline__ void select_threshold(uint64_t rb, int64_t d, int64_t k, int lane,
+                                                 uint64_t* thresh, int64_t* take_eq) {
+  uint64_t prefix = 0;
+  int64_t remaining = k;
+  if (d <= kRegSlots) {
+    uint64_t key[kRegKeys];
+    bool valid[kRegKeys];
+#pragma unroll
+    for (int r = 0; r < kRegKeys; ++r) {
+      const int64_t p = r * 64 + lane;
+      valid[r] = p < d;
+      key[r] = sample_slot_key(rb, p);
+    }
+    for (int bit = 63; bit >= 0; --bit) {
+      int64_t zeros = 0;
+#pragma unroll
+      for (int r = 0; r < kRegKeys; ++r)
+        zeros += __popcll(__ballot(valid[r] && ((key[r] ^ prefix) >> bit) == 0));
+      if (remaining > zeros) {
+        prefix |= uint64_t(1) << bit;
+        remaining -= zeros;
+      }
+    }
+  } else {
+    for (int bit = 63; bit >= 0; --bit) {
+      int64_t zeros = 0;
+      for (int64_t p = lane; p < d; p += 64)
+        zeros += ((sample_slot_key(rb, p) ^ prefix) >> bit) == 0 ? 1 : 0;
+      zeros = wave_sum(zeros);
+      if (remaining > zeros) {
+        prefix |= uint64_t(1) << bit;
+        remaining -= zeros;
+      }
+    }
+  }
+  *thresh = prefix;
+  *take_eq = remaining;
+}
+
+// Calls f(selected, p, rank) for the positions p = 0..d-1 of a row, a stride of
+// 64 at a time and every lane of the wave in every call (so f may ballot);
+// rank is the number of selected positions below p.
+template <typename F>
+__device__ __forceinline__ void for_selected(uint64_t rb, int64_t d, int64_t k, int lane, F&& f) {
+  if (k <= 0 || d <= 0) return;
+  if (d <= k) {
+    for (int64_t s = 0; s < d; s += 64) f(s + lane < d, s + lane, s + lane);
+    return;
+  }
+  uint64_t thresh;
+  int64_t take_eq;
+  select_threshold(rb, d, k, lane, &thresh, &take_eq);
+  const u64 below = (u64(1) << lane) - 1;
+  int64_t out = 0, eq_seen = 0;
+  for (int64_t s = 0; s < d && out < k; s += 64) {
+    const int64_t p = s + lane;
+    const uint64_t key = sample_slot_key(rb, p);
+    const bool eq = p < d && key == thresh;
+    const u64 eq_mask = __ballot(eq);
+    const bool sel = p < d && (key < thresh ||
+                               (eq && eq_seen + __popcll(eq_mask & below) < take_eq));
+    const u64 sel_mask = __ballot(sel);
+    f(sel, p, out + __popcll(sel_mask & below));
+    out += __popcll(sel_mask);
+    eq_seen += __popcll(eq_mask);
+  }
+}
+
+// Appends the winners' ids to next[] behind *count: one atomicAdd per wave.
+__device__ __forceinline__ void wave_append(bool win, int64_t id, int64_t* count, int64_t* next,
+                                            int64_t cap, int lane) {
+  const u64 mask = __ballot(win);
+  if (mask == 0) return;  // the whole wave
+  long long base = 0;
+  if (lane == 0)
+    base = static_cast<long long>(
+        atomicAdd(reinterpret_cast<u64*>(count), static_cast<u64>(__popcll(mask))));
+  base = __shfl(base, 0, 64);
+  const int64_t pos = base + __popcll(mask & ((u64(1) << lane) - 1));
+  if (win && pos < cap) next[pos] = id;
+}
+
+__global__ __launch_bounds__(kThreads) void ns_seed_kernel(int64_t N, int64_t n,
+                                                           const int64_t* seeds, int32_t* layer,
+                                                           int64_t* front, int64_t* status) {
+  const int64_t i = block_linear() * kThreads + threadIdx.x;
+  const int lane = threadIdx.x & 63;
+  bool bad = false, win = false;
+  int64_t v = -1;
+  if (i < n) {
+    v = seeds[i];
+    if (v < 0 || v >= N) bad = true;  // counted, never used as an index
+    else win = atomicCAS(layer + v, -1, 0) == -1;
+  }
+  const u64 bad_mask = __ballot(bad);
+  if (bad_mask != 0 && lane == 0)
+    atomicAdd(reinterpret_cast<u64*>(status + 1), static_cast<u64>(__popcll(bad_mask)));
+  wave_append(win, v, status, front, n, lane);
+}
+
+struct HopArgs {
+  int64_t N, nnz, f, k, cap;
+  int32_t next_layer;
+  uint64_t seed;
+  const int64_t* indptr;
+  const int32_t* indices;
+  const int64_t* front;
+  int32_t* layer;
+  int64_t* next;
+  int64_t* status;
+};
+
+__global__ __launch_bounds__(kThreads) void ns_hop_kernel(HopArgs a) {
+  const int64_t i = block_linear() * kWaves + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (i >= a.f) return;  // the whole wave
+  const int64_t v = a.front[i];
+  if (v < 0 || v >= a.N) return;
+  int64_t beg, end;
+  row_range(a.indptr, a.nnz, v, &beg, &end);
+  const int64_t d = end - beg;
+  if (d == 0 || a.k <= 0) return;
+  if (lane == 0)
+    atomicAdd(reinterpret_cast<u64*>(a.status + 2), static_cast<u64>(d < a.k ? d : a.k));
+  for_selected(sample_row_base(a.seed, v), d, a.k, lane,
+               [&](bool sel, int64_t p, int64_t) {
+                 const int32_t nbr = sel ? a.indices[beg + p] : -1;
+                 // a neighbour outside [0, N) is not followed
+                 const bool ok = sel && static_cast<uint32_t>(nbr) < static_cast<uint64_t>(a.N);
+                 const bool win = ok && atomicCAS(a.layer + nbr, -1, a.next_layer) == -1;
+                 wave_append(win, nbr, a.status, a.next, a.cap, lane);
+               });
+}
+
+struct FinalArgs {
+  int64_t N, nnz, V, m, k;
+  int32_t num_hops, in_dir;
+  uint64_t seed;
+  const int64_t* indptr;
+  const int32_t* indices;
+  const int64_t* eid;
+  const int32_t* layer;
+  const int32_t* pos;
+  int64_t* cnt;
+  int64_t* base;
+  int64_t* vertices;
+  int64_t* layers;
+  int64_t* sub_src;
+  int64_t* sub_dst;
+  int64_t* parent_eid;
+};
+
+__global__ __launch_bounds__(kThreads) void ns_compact_kernel(FinalArgs a) {
+  const int64_t v = block_linear() * kThreads + threadIdx.x;
+  if (v >= a.N) return;
+  const int32_t l = a.layer[v];
+  if (l < 0) return;
+  const int64_t i = int64_t(a.pos[v]) - 1;
+  if (i < 0 || i >= a.V) return;
+  int64_t c = 0;
+  if (l < a.num_hops) {
+    int64_t beg, end;
+    row_range(a.indptr, a.nnz, v, &beg, &end);
+    c = end - beg < a.k ? end - beg : a.k;
+  }
+  a.vertices[i] = v;
+  a.layers[i] = l;
+  a.cnt[i] = c;
+}
+
+__global__ __launch_bounds__(kThreads) void ns_fill_kernel(FinalArgs a) {
+  const int64_t i = block_linear() * kWaves + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (i >= a.V) return;  // the whole wave
+  const int64_t v = a.vertices[i];
+  if (v < 0 || v >= a.N || a.layers[i] >= a.num_hops) return;
+  int64_t beg, end;
+  row_range(a.indptr, a.nnz, v, &beg, &end);
+  const int64_t out = a.base[i];
+  for_selected(sample_row_base(a.seed, v), end - beg, a.k, lane,
+               [&](bool sel, int64_t p, int64_t rank) {
+                 const int64_t o = out + rank;
+                 if (!sel || o < 0 || o >= a.m) return;
+                 const int32_t nbr = a.indices[beg + p];
+                 int64_t nid = -1;  // a neighbour outside [0, N) was not followed
+                 if (static_cast<uint32_t>(nbr) < static_cast<uint64_t>(a.N) && a.layer[nbr] >= 0)
+                   nid = int64_t(a.pos[nbr]) - 1;
+                 a.sub_src[o] = a.in_dir ? nid : i;
+                 a.sub_dst[o] = a.in_dir ? i : nid;
+                 a.parent_eid[o] = a.eid[beg + p];
+               });
+}
+
+void check_sizes(int64_t N, int64_t nnz) {
+  DGLHIP_CHECK(N >= 0 && nnz >= 0, "negative size");
+  DGLHIP_CHECK(N < (int64_t(1) << 31), "node ids are 32-bit in the layer map");
+}
+
+void check_not_capturing(hipStream_t stream) {
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  HIP_CALL(hipStreamIsCapturing(stream, &cap));
+  DGLHIP_CHECK(cap == hipStreamCaptureStatusNone,
+               "neighbour sampling reads every frontier's size on the host and cannot be "
+               "captured");
+}
+
+}  // namespace
+
+}  // namespace dglhip
+
+using namespace dglhip;
+
+extern "C" {
+
+int64_t dglhip_neighbor_sample_workspace_bytes(int64_t num_nodes, int64_t num_vertices) {
+  try {
+    check_sizes(num_nodes, 0);
+    DGLHIP_CHECK(num_vertices >= 0 && num_vertices <= num_nodes,
+                 "bad vertex count " << num_vertices);
+    return Layout(num_nodes, num_vertices).total;
+  } catch (const std::exception& e) {
+    set_last_error(e.what());
+    return -1;
+  }
+}
+
+int dglhip_neighbor_sample_init_device(int64_t num_nodes, const int64_t* seeds, int64_t num_seeds,
+                                       int32_t* layer, int64_t* frontier, int64_t* status,
+                                       void* stream_) {
+  API_BEGIN();
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  check_sizes(num_nodes, 0);
+  check_not_capturing(stream);
+  DGLHIP_CHECK(num_seeds >= 0 && num_seeds < (int64_t(1) << 31),
+               "bad number of seeds " << num_seeds);
+  DGLHIP_CHECK(status && (num_nodes == 0 || layer) && (num_seeds == 0 || (seeds && frontier)),
+               "null pointer argument");
+  HIP_CALL(hipMemsetAsync(status, 0, 4 * sizeof(int64_t), stream));
+  if (num_nodes > 0)
+    HIP_CALL(hipMemsetAsync(layer, 0xFF, size_t(num_nodes) * sizeof(int32_t), stream));
+  if (num_seeds > 0) {
+    hipLaunchKernelGGL(ns_seed_kernel, grid_1d((num_seeds + kThreads - 1) / kThreads),
+                       dim3(kThreads), 0, stream, num_nodes, num_seeds, seeds, layer, frontier,
+                       status);
+    HIP_CALL(hipGetLastError());
+  }
+  API_END();
+}
+
+int dglhip_neighbor_sample_hop_device(int64_t num_nodes, int64_t nnz, const int64_t* indptr,
+                                      const int32_t* indices, const int64_t* frontier,
+                                      int64_t frontier_len, int hop, int64_t fanout, uint64_t seed,
+                                      int32_t* layer, int64_t* next, int64_t next_capacity,
+                                      int64_t* status, void* stream_) {
+  API_BEGIN();
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  check_sizes(num_nodes, nnz);
+  check_not_capturing(stream);
+  DGLHIP_CHECK(num_nodes >= 1 && frontier_len >= 1 && frontier_len <= num_nodes && hop >= 0 &&
+                   hop < (1 << 30) && fanout >= 0 && next_capacity >= 0,
+               "bad hop " << hop << ": " << frontier_len << " rows, fan-out " << fanout);
+  DGLHIP_CHECK(indptr && frontier && layer && status && (nnz == 0 || indices) &&
+                   (next_capacity == 0 || next),
+               "null pointer argument");
+  HIP_CALL(hipMemsetAsync(status, 0, 4 * sizeof(int64_t), stream));
+  HopArgs a;
+  a.N = num_nodes; a.nnz = nnz; a.f = frontier_len; a.k = fanout; a.cap = next_capacity;
+  a.next_layer = hop + 1; a.seed = seed;
+  a.indptr = indptr; a.indices = indices; a.front = frontier; a.layer = layer; a.next = next;
+  a.status = status;
+  hipLaunchKernelGGL(ns_hop_kernel, grid_1d((frontier_len + kWaves - 1) / kWaves), dim3(kThreads),
+                     0, stream, a);
+  HIP_CALL(hipGetLastError());
+  API_END();
+}
+
+int dglhip_neighbor_sample_final_device(int64_t num_nodes, int64_t nnz, const int64_t* indptr,
+                                        const int32_t* indices, const int64_t* eid,
+                                        int in_direction, int num_hops, int64_t fanout,
+                                        uint64_t seed, const int32_t* layer, int64_t num_vertices,
+                                        int64_t num_edges, int64_t* vertices, int64_t* layers,
+                                        int64_t* sub_src, int64_t* sub_dst, int64_t* parent_eid,
+                                        void* workspace, int64_t workspace_bytes, void* stream_) {
+  API_BEGIN();
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  check_sizes(num_nodes, nnz);
+  DGLHIP_CHECK(num_vertices >= 0 && num_vertices <= num_nodes && num_edges >= 0 &&
+                   num_edges <= nnz && num_hops >= 0 && fanout >= 0,
+               "bad sample of " << num_vertices << " vertices, " << num_edges << " edges");
+  if (num_vertices == 0) return 0;
+  DGLHIP_CHECK(indptr && layer && vertices && layers && workspace, "null pointer argument");
+  DGLHIP_CHECK(num_edges == 0 || (indices && eid && sub_src && sub_dst && parent_eid),
+               "null pointer argument");
+  const Layout L(num_nodes, num_vertices);
+  DGLHIP_CHECK(workspace_bytes >= L.total, "workspace of " << workspace_bytes << " B, "
+                                                           << L.total << " needed");
+  char* ws = static_cast<char*>(workspace);
+  FinalArgs a;
+  a.N = num_nodes; a.nnz = nnz; a.V = num_vertices; a.m = num_edges; a.k = fanout;
+  a.num_hops = num_hops; a.in_dir = in_direction ? 1 : 0; a.seed = seed;
+  a.indptr = indptr; a.indices = indices; a.eid = eid; a.layer = layer;
+  int32_t* pos = reinterpret_cast<int32_t*>(ws + L.pos);
+  a.pos = pos;
+  a.cnt = reinterpret_cast<int64_t*>(ws + L.cnt);
+  a.base = reinterpret_cast<int64_t*>(ws + L.base);
+  a.vertices = vertices; a.layers = layers;
+  a.sub_src = sub_src; a.sub_dst = sub_dst; a.parent_eid = parent_eid;
+  size_t scan_len = size_t(L.scan_len);
+  HIP_CALL(rocprim::inclusive_scan(ws + L.scan, scan_len, VisitedIter(layer, IsVisited()), pos,
+                                   size_t(num_nodes), rocprim::plus<int32_t>(), stream));
+  // a vertex count that is not the map's leaves rows unwritten: defined values
+  HIP_CALL(hipMemsetAsync(a.cnt, 0, size_t(num_vertices) * sizeof(int64_t), stream));
+  HIP_CALL(hipMemsetAsync(vertices, 0xFF, size_t(num_vertices) * sizeof(int64_t), stream));
+  HIP_CALL(hipMemsetAsync(layers, 0xFF, size_t(num_vertices) * sizeof(int64_t), stream));
+  HIP_CALL(hipMemsetAsync(a.base, 0, sizeof(int64_t), stream));
+  hipLaunchKernelGGL(ns_compact_kernel, grid_1d((num_nodes + kThreads - 1) / kThreads),
+                     dim3(kThreads), 0, stream, a);
+  HIP_CALL(hipGetLastError());
+  if (num_edges > 0) {
+    scan_len = size_t(L.scan_len);
+    HIP_CALL(rocprim::inclusive_scan(ws + L.scan, scan_len, static_cast<const int64_t*>(a.cnt),
+                                     a.base + 1, size_t(num_vertices), rocprim::plus<int64_t>(),
+                                     stream));
+    hipLaunchKernelGGL(ns_fill_kernel, grid_1d((num_vertices + kWaves - 1) / kWaves),
+                       dim3(kThreads), 0, stream, a);
+    HIP_CALL(hipGetLastError());
+  }
+  API_END();
+}
+
+}  // extern "C"

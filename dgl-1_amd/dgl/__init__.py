@@ -24,4 +24,5 @@ from .propagate import *  # noqa: F401,F403
 from .udf import EdgeBatch, NodeBatch  # noqa: F401
 from .runtime import ir  # noqa: F401
 from . import nn  # noqa: F401
+from . import contrib  # noqa: F401
 from ._ffi import list_global_names as list_global_func_names  # noqa: F401

@@ -236,6 +236,19 @@ def _load():
         "dglhip_traversal_level_device": (_c_int, [_c_int, _c_i64, _c_i64] + [_vp] * 4 +
                                           [_c_i64] * 3 + [_vp] * 5 + [_c_i64, _vp, _c_i64, _vp,
                                                                       _vp]),
+        "dglhip_sample_mix": (_c_u64, [_c_u64]),
+        "dglhip_sample_key": (_c_u64, [_c_u64, _c_i64, _c_i64]),
+        "dglhip_neighbor_sample_workspace_bytes": (_c_i64, [_c_i64, _c_i64]),
+        "dglhip_neighbor_sample_init_device": (_c_int, [_c_i64, _vp, _c_i64, _vp, _vp, _vp, _vp]),
+        "dglhip_neighbor_sample_hop_device": (_c_int, [_c_i64, _c_i64, _vp, _vp, _vp, _c_i64,
+                                                       _c_int, _c_i64, _c_u64, _vp, _vp, _c_i64,
+                                                       _vp, _vp]),
+        "dglhip_neighbor_sample_final_device": (_c_int, [_c_i64, _c_i64, _vp, _vp, _vp, _c_int,
+                                                         _c_int, _c_i64, _c_u64, _vp, _c_i64,
+                                                         _c_i64] + [_vp] * 6 + [_c_i64, _vp]),
+        "dglhip_neighbor_sample_host": (_c_int, [_c_i64, _c_i64, _vp, _vp, _vp, _c_int, _vp,
+                                                 _c_i64, _c_int, _c_i64, _c_u64, _vp]),
+        "dglhip_neighbor_sample_host_fetch": (_c_int, [_c_i64, _c_i64] + [_vp] * 5),
         "dglhip_xent_workspace_floats": (_c_int, []),
         "dglhip_xent_fwd_device": (_c_int, [_c_i64, _c_i64, _vp, _c_i64, _vp, _vp, _vp, _vp, _vp]),
         "dglhip_xent_bwd_device": (_c_int, [_c_i64, _c_i64, _vp, _c_i64, _vp, _vp, _vp, _vp,

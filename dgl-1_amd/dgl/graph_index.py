@@ -17,6 +17,7 @@ built from it per device (kernel.from_coo); all are dropped on mutation.
 from __future__ import absolute_import
 
 import ctypes
+import os
 
 import numpy as np
 import torch
@@ -311,6 +312,77 @@ class GraphIndex(object):
         nid = v.detach().to(torch.int64).reshape(-1)
         return SubgraphIndex(self, nid, eid, device_coo=(nid.numel(), src, dst))
 
+    # -- neighbour sampling (graph_index.py:664-678, 1018-1027) ------------------
+    def neighbor_sampling(self, seed_ids, expand_factor, num_hops, neighbor_type, node_prob,
+                          seed=None):
+        """One sampled ``num_hops``-hop subgraph per seed set of the list
+        ``seed_ids``: each expanded vertex keeps at most ``expand_factor`` of
+        its 'in' or 'out' neighbours, drawn uniformly.
+
+        Seed sets on the host with ``seed`` None go to the native sampler
+        (``_CAPI_DGLGraphUniformSampling*``), which draws afresh on every call.
+        Seed sets on a ROCm device, or any with a ``seed``, take the stateless
+        rule of kernel.neighbor_sample over the cached adjacency on the seeds'
+        device; subgraph ``i`` of the call is drawn under ``mix(seed + i)``,
+        and a device call without a ``seed`` draws a fresh one. That route
+        leaves a subgraph's ids and edge list where the seeds are. Every
+        returned index carries the layer of its nodes as ``induced_layers``."""
+        if not self._readonly:
+            raise NotImplementedError("neighbor sampling only supports read-only graphs.")
+        if node_prob is not None:
+            raise NotImplementedError("non-uniform neighbor sampling is not supported.")
+        if neighbor_type not in ("in", "out"):
+            raise DGLError("neighbor_type must be 'in' or 'out', got %r" % (neighbor_type,))
+        if isinstance(expand_factor, bool) or not isinstance(expand_factor, (int, np.integer)):
+            raise DGLError("expand_factor must be an integer, got %r" % (expand_factor,))
+        expand_factor, num_hops = int(expand_factor), int(num_hops)
+        if expand_factor < 0 or num_hops < 0:
+            raise DGLError("invalid sampling parameters: fan-out %d, %d hops"
+                           % (expand_factor, num_hops))
+        seed_ids = list(seed_ids)
+        if len(seed_ids) == 0:
+            return []
+        on_device = [isinstance(s, torch.Tensor) and s.is_cuda for s in seed_ids]
+        if seed is None and not any(on_device):
+            return self._native_sampling([_as_i64(s) for s in seed_ids], expand_factor, num_hops,
+                                         neighbor_type)
+        if seed is None:
+            seed = int.from_bytes(os.urandom(8), "little")
+        out = []
+        for i, ids in enumerate(seed_ids):
+            ctx = ids.device if on_device[i] else torch.device("cpu")
+            if not on_device[i]:
+                ids = _as_i64(ids)
+            adj = self.adjacency(ctx)
+            in_dir = neighbor_type == "in"
+            vertices, layers, src, dst, eid = kernel.neighbor_sample(
+                adj.fwd if in_dir else adj.bwd, ids, num_hops, expand_factor,
+                kernel.sample_mix(int(seed) + i), in_dir=in_dir)
+            sgi = SubgraphIndex(self, vertices, eid, device_coo=(vertices.numel(), src, dst))
+            sgi.induced_layers = layers
+            out.append(sgi)
+        return out
+
+    def _native_sampling(self, seed_ids, expand_factor, num_hops, neighbor_type):
+        n = len(seed_ids)
+        # the registry holds the sampler at 1, 2, 4, ..., 128 seed arrays: pad
+        # with empty ones up to the next width and say how many are real
+        out = []
+        for b in range(0, n, 128):
+            part = seed_ids[b:b + 128]
+            width = 1
+            while width < len(part):
+                width *= 2
+            pad = [torch.zeros(0, dtype=torch.int64) for _ in range(width - len(part))]
+            api = "_CAPI_DGLGraphUniformSampling" + ("" if width == 1 else str(width))
+            f = _call(api, self._h(), *(part + pad + [neighbor_type, num_hops, expand_factor,
+                                                      len(part)]))
+            for i in range(len(part)):
+                sgi = SubgraphIndex(self, f(width + i), f(2 * width + i), handle=f(i))
+                sgi.induced_layers = f(3 * width + i)
+                out.append(sgi)
+        return out
+
     # -- traversals (python/dgl/traversal.py -> traversal._CAPI_*) --------------
     # Each returns (ids, sections): the frontiers are consecutive runs of the
     # int64 tensor ``ids`` whose lengths are the Python list ``sections``.
@@ -393,10 +465,12 @@ class SubgraphIndex(GraphIndex):
 
     Made either from the handle the native index returned, or from the edge
     list ``device_coo = (n, src, dst)`` a device extraction left on the GPU
-    (GraphIndex.node_subgraph_device). In the second form the sizes and the
-    g-SpMM CSRs on that device come straight from the device arrays, and the
-    native index is only built, from one download of the edge list, when a
-    query needs it (:attr:`has_native_index`)."""
+    (GraphIndex.node_subgraph_device under a mutable parent, the seeded route
+    of GraphIndex.neighbor_sampling under a read-only one; the native index
+    built on demand is mutable or immutable to match). In the second form the
+    sizes and the g-SpMM CSRs on that device come straight from the device
+    arrays, and the native index is only built, from one download of the edge
+    list, when a query needs it (:attr:`has_native_index`)."""
 
     def __init__(self, parent, induced_nodes, induced_edges, handle=None, device_coo=None):
         # not GraphIndex.__init__: that creates a native index at once
@@ -408,6 +482,7 @@ class SubgraphIndex(GraphIndex):
         self._induced_nodes = induced_nodes
         self._induced_edges = induced_edges
         self._dev_coo = None
+        self.induced_layers = None  # the hop of every node of a sampled subgraph
         if handle is not None:
             self._sync_sizes()
         else:
@@ -419,6 +494,13 @@ class SubgraphIndex(GraphIndex):
         if self._handle is None:
             # the extraction validated the endpoints: straight into a new index
             src, dst = (t.cpu() for t in self._dev_coo)
+            if self._readonly:
+                # a sampled subgraph of a read-only parent: an immutable index
+                # whose edge ids are the positions in the edge list
+                self._handle = _call("_CAPI_DGLGraphCreate", src, dst,
+                                     torch.arange(self._m, dtype=torch.int64),
+                                     int(self._multigraph), self._n, 1)
+                return ("handle", self._handle)
             h = _call("_CAPI_DGLGraphCreateMutable", int(self._multigraph))
             self._handle = h
             _call("_CAPI_DGLGraphAddVertices", ("handle", h), self._n)
@@ -459,8 +541,10 @@ class SubgraphIndex(GraphIndex):
         key = ("adj", str(ctx))
         if key not in self._cache:
             src, dst = self._dev_coo
-            self._cache[key] = kernel.from_coo(self._n, self._n, dst, src, kernel.ORDER_EID, ctx,
-                                               validate=False)
+            # (slots in the order the index itself would give: edge ids under a
+            # mutable parent, (dst, src) under a read-only one)
+            self._cache[key] = kernel.from_coo(self._n, self._n, dst, src, self._slot_order(),
+                                               ctx, validate=False)
         return self._cache[key]
 
     def incidence_in(self, ctx):

@@ -2919,3 +2919,123 @@ def topological_frontiers(csr, opposite):
     if end != N:
         raise DGLError("Error in topological traversal: loop detected in the given graph.")
     return queue, loop.sections
+
+
+# ---------------------------------------------------------------------------
+# Uniform neighbour sampling (csrc/neighbor_sample.hip, neighbor_sample_host.cc)
+# ---------------------------------------------------------------------------
+SAMPLE_REG_SLOTS = 256  # DGLHIP_SAMPLE_REG_SLOTS: the longest row selected from registers
+_U64 = (1 << 64) - 1
+
+
+def sample_mix(z):
+    """The hash of the sampling rule (csrc/sample_key.h) of the integer ``z``
+    taken modulo 2^64."""
+    return int(LIB.dglhip_sample_mix(int(z) & _U64))
+
+
+def _neighbor_sample_host(csr, seeds, num_hops, k, seed, in_dir):
+    seeds = seeds.cpu()
+    N, nnz = csr.num_rows, csr.nnz
+    sizes = torch.zeros(2, dtype=torch.int64)
+    check_call(LIB.dglhip_neighbor_sample_host(
+        N, nnz, ptr(csr.indptr), ptr(csr.indices) if nnz else None,
+        ptr(csr.eid) if nnz else None, int(in_dir), ptr(seeds) if seeds.numel() else None,
+        seeds.numel(), num_hops, k, seed, ptr(sizes)))
+    nv, m = sizes.tolist()
+    nodes = torch.empty(2, nv, dtype=torch.int64)
+    edges = torch.empty(3, m, dtype=torch.int64)
+    check_call(LIB.dglhip_neighbor_sample_host_fetch(
+        nv, m, ptr(nodes[0]), ptr(nodes[1]), ptr(edges[0]), ptr(edges[1]), ptr(edges[2])))
+    return nodes[0], nodes[1], edges[0], edges[1], edges[2]
+
+
+def neighbor_sample(csr, seeds, num_hops, k, seed, in_dir=True, timings=None):
+    """The ``num_hops``-hop neighbourhood of the int64 ids ``seeds`` sampled
+    at fan-out ``k`` over ``csr`` (rows = the vertex expanded:
+    ``SparseAdj.fwd`` with ``in_dir``, ``.bwd`` without) by the stateless rule
+    of csrc/sample_key.h under the 64-bit ``seed``: ``(vertices, layers,
+    sub_src, sub_dst, parent_eid)``, int64 on the device of ``csr``.
+
+    ``vertices`` are the visited parent ids ascending and ``layers`` the hop
+    that reached each (seeds: 0); the edges are the selected slots of every
+    vertex of layer < num_hops in ascending id, each row in ascending
+    position, as endpoints in ``vertices`` plus the parent edge id. The arrays
+    depend on the arguments alone: the HIP route (a CSR on a ROCm device) and
+    the host twin (a CSR in host memory) give the same ones, bit for bit.
+
+    On a device there is one host read for the seeds and one per hop, so it
+    cannot run while the current stream is being captured. A seed outside the
+    graph raises DGLError. ``timings`` (a dict) receives device events around
+    the hop loop and the final stage."""
+    num_hops, k, seed = int(num_hops), int(k), int(seed) & _U64
+    if num_hops < 0 or k < 0:
+        raise DGLError("invalid sampling parameters: %d hops, fan-out %d" % (num_hops, k))
+    if seeds.dtype.is_floating_point or seeds.dtype == torch.bool:
+        raise DGLError("Index data must be an integer tensor, got %s" % seeds.dtype)
+    dev = csr.device
+    seeds = seeds.detach().to(dtype=torch.int64).reshape(-1).contiguous()
+    if dev.type != "cuda":
+        return _neighbor_sample_host(csr, seeds, num_hops, k, seed, in_dir)
+    if torch.cuda.is_current_stream_capturing():  # before anything is launched
+        raise DGLError("neighbour sampling reads every frontier's size on the host: it cannot "
+                       "run while a stream is being captured")
+    seeds = seeds.to(dev)
+    N, nnz, n = csr.num_rows, csr.nnz, seeds.numel()
+    stream = _stream_of(dev)
+    status = torch.empty(4, dtype=torch.int64, device=dev)
+    host = torch.empty(4, dtype=torch.int64, pin_memory=True)
+
+    def read_status():
+        host.copy_(status, non_blocking=True)
+        torch.cuda.current_stream(dev).synchronize()
+        return host.tolist()
+
+    if timings is not None:
+        marks = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        marks[0].record()
+    layer = torch.empty(N, dtype=torch.int32, device=dev)
+    front = torch.empty(n, dtype=torch.int64, device=dev)
+    check_call(LIB.dglhip_neighbor_sample_init_device(
+        N, ptr(seeds) if n else None, n, ptr(layer) if N else None, ptr(front) if n else None,
+        ptr(status), stream))
+    size, invalid, _, _ = read_status()
+    if invalid:
+        raise DGLError("Invalid vertex: %d of the %d seeds are not in a graph of %d nodes"
+                       % (invalid, n, N))
+    nv, m = size, 0
+    for hop in range(num_hops):
+        if size == 0 or k == 0:
+            break
+        cap = min(N - nv, size * k)
+        nxt = torch.empty(cap, dtype=torch.int64, device=dev)
+        check_call(LIB.dglhip_neighbor_sample_hop_device(
+            N, nnz, ptr(csr.indptr), ptr(csr.indices) if nnz else None, ptr(front), size, hop, k,
+            seed, ptr(layer), ptr(nxt) if cap else None, cap, ptr(status), stream))
+        new_size, _, edges, _ = read_status()
+        if new_size > cap or edges > nnz - m:
+            raise DGLError("device sampling: inconsistent hop (%d of %d frontier slots, %d "
+                           "edges)" % (new_size, cap, edges))
+        front, size = nxt, new_size
+        nv += new_size
+        m += edges
+    if timings is not None:
+        marks[1].record()
+    nodes = torch.empty(2, nv, dtype=torch.int64, device=dev)
+    out = torch.empty(3, m, dtype=torch.int64, device=dev)
+    if nv:
+        nbytes = LIB.dglhip_neighbor_sample_workspace_bytes(N, nv)
+        if nbytes < 0:
+            check_call(-1)
+        ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
+        check_call(LIB.dglhip_neighbor_sample_final_device(
+            N, nnz, ptr(csr.indptr), ptr(csr.indices) if nnz else None,
+            ptr(csr.eid) if m else None, int(bool(in_dir)), num_hops, k, seed, ptr(layer), nv, m,
+            ptr(nodes[0]), ptr(nodes[1]), ptr(out[0]) if m else None, ptr(out[1]) if m else None,
+            ptr(out[2]) if m else None, ptr(ws), int(nbytes), stream))
+    if timings is not None:
+        marks[2].record()
+        marks[2].synchronize()
+        timings["hops_ms"] = marks[0].elapsed_time(marks[1])
+        timings["final_ms"] = marks[1].elapsed_time(marks[2])
+    return nodes[0], nodes[1], out[0], out[1], out[2]

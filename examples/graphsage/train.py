@@ -21,6 +21,14 @@ bytes through the g-SpMM (same result up to fp32 rounding).
   python examples/graphsage/train.py --dataset reddit --gpu 0
   torchrun --nproc-per-node 8 --master-addr 127.0.0.1 examples/graphsage/train.py --dist \\
       --graph rmat --rmat-scale 24
+
+``--sample FANOUT`` trains on mini-batches instead: per batch of training
+seeds the sampled neighbourhood (dgl.contrib.sampling.NeighborSampler, one hop
+per layer, FANOUT in-neighbours per node) is built, on the GPU when the model
+is there, the features are gathered with ``copy_from_parent``, the model runs
+on the subgraph and the loss is taken on the seed rows.
+
+  python examples/graphsage/train.py --dataset cora --sample 10 --batch-size 256
 """
 import argparse
 import os
@@ -36,7 +44,9 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
                                 "dgl-1_amd"))
 import dgl.function as fn  # noqa: E402
 from dgl import DGLGraph, data, kernel  # noqa: E402
+from dgl.contrib.sampling import NeighborSampler  # noqa: E402
 from dgl.distributed import PartitionedGraph, balanced_bounds  # noqa: E402
+from dgl.graph_index import _from_edges  # noqa: E402
 from dgl.nn.pytorch import NodeLinear, sage_dense, weighted_cross_entropy  # noqa: E402
 
 
@@ -87,8 +97,63 @@ def graph_and_data(args, device):
     return src, dst, ds.num_nodes, ds.features, ds.labels, ds.train_mask, ds.num_labels
 
 
+def run_sampled(args, device, src, dst, n, feats, labels, train, ncls):
+    """Mini-batch training over sampled neighbourhoods (``--sample``)."""
+    g = DGLGraph(_from_edges(n, src.cpu(), dst.cpu(), True, True), multigraph=True,
+                 readonly=True)
+    g.ndata["feat"] = feats
+    g.ndata["label"] = labels
+    # seeds on the model's device: a ROCm device samples there
+    seeds = torch.nonzero(train).reshape(-1).to(device)
+    num_hops = args.n_layers + 1  # one hop per layer
+    torch.manual_seed(args.seed)
+    model = SAGE(feats.shape[1], args.n_hidden, ncls, args.n_layers, args.dropout).to(device)
+    opt = torch.optim.Adam(model.parameters(), lr=args.lr)
+    dur, losses, batches, sub_edges = [], [], 0, 0
+    for epoch in range(args.n_epochs):
+        model.train()
+        if device.type == "cuda":
+            torch.cuda.synchronize()
+        t0 = time.time()
+        sampler = NeighborSampler(g, args.batch_size, args.sample, num_hops=num_hops,
+                                  neighbor_type="in", seed_nodes=seeds, shuffle=True,
+                                  seed=args.seed + epoch)
+        for sg, _ in sampler:
+            if args.max_batches and batches >= args.max_batches:
+                break
+            sg.copy_from_parent()
+
+            def aggregate(h):
+                sg.ndata["h"] = h
+                sg.update_all(fn.copy_src("h", "m"), fn.mean("m", "neigh"))
+                return sg.ndata.pop("neigh")
+
+            logits = model(sg.ndata["feat"], aggregate)
+            is_seed = sg._graph.induced_layers.to(device) == 0
+            loss = F.cross_entropy(logits[is_seed], sg.ndata["label"][is_seed])
+            opt.zero_grad()
+            loss.backward()
+            opt.step()
+            losses.append(float(loss.item()))
+            batches += 1
+            sub_edges += sg.number_of_edges()
+        if device.type == "cuda":
+            torch.cuda.synchronize()
+        dur.append(time.time() - t0)
+        if args.max_batches and batches >= args.max_batches:
+            break
+    mean = sum(dur) / len(dur)
+    state = {k: v.detach().cpu() for k, v in model.state_dict().items()}
+    return {"graph": args.graph if args.graph == "rmat" else args.dataset, "world": 1,
+            "epoch_s": mean, "edges": g.number_of_edges(), "sample": args.sample,
+            "batches": batches, "sampled_edges": sub_edges, "loss": losses[-1],
+            "losses": losses, "state": state}
+
+
 def run(args):
     distributed = args.dist
+    if args.sample and distributed:
+        raise ValueError("--sample trains in one process: drop --dist")
     if distributed:
         if not dist.is_initialized():
             backend = args.dist_backend or ("nccl" if torch.cuda.is_available() else "gloo")
@@ -105,6 +170,8 @@ def run(args):
         device = torch.device("cpu") if args.gpu < 0 else torch.device("cuda", args.gpu)
 
     src, dst, n, feats, labels, train, ncls = graph_and_data(args, device)
+    if args.sample:
+        return run_sampled(args, device, src, dst, n, feats, labels, train, ncls)
     n_train_global = int(train.sum())
     if distributed:
         bounds = balanced_bounds(torch.bincount(dst, minlength=n), world)
@@ -201,12 +268,19 @@ def parser():
     p.add_argument("--row-split", default=None,
                    help="heavy-row policy of the g-SpMM (off / auto / a chunk length; "
                         "default: the library's, dgl.kernel.set_row_split)")
+    p.add_argument("--sample", type=int, default=0, metavar="FANOUT",
+                   help="mini-batch training on sampled neighbourhoods with this many "
+                        "in-neighbours per node and hop (0: full-graph training)")
+    p.add_argument("--batch-size", type=int, default=1000, help="--sample: seeds per batch")
+    p.add_argument("--max-batches", type=int, default=0,
+                   help="--sample: stop after this many batches (0: all epochs)")
     return p
 
 
 if __name__ == "__main__":
     res = run(parser().parse_args())
     res.pop("state")
+    res.pop("losses", None)
     if res["world"] == 1 or dist.get_rank() == 0:
         print(res)
     if dist.is_initialized():

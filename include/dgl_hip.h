@@ -594,6 +594,92 @@ int dglhip_traversal_level_device(int mode, int64_t num_nodes, int64_t nnz, cons
                                   int64_t workspace_bytes, int64_t* status, void* stream);
 
 /* ------------------------------------------------------------------------ */
+/* Uniform neighbour sampling on the device (csrc/neighbor_sample.hip): the  */
+/* reference's ImmutableGraph::SampleSubgraph + CompactSubgraph              */
+/* (src/graph/immutable_graph.cc:792-1011) over a CSR that is already on the */
+/* device: indptr int64[num_nodes + 1], indices int32[nnz], eid int64[nnz].  */
+/* Row v holds the edges the sample follows from v: the destination-major    */
+/* CSR for neighbour type 'in', the source-major one for 'out'.              */
+/* The draw is stateless (csrc/sample_key.h): slot p of row v has the key    */
+/*   key(seed, v, p) = mix(mix(mix(seed) ^ v) ^ p), mix = splitmix64's       */
+/*   finaliser (dglhip_sample_mix; mix(0) = 0xE220A8397B1DCDAF),             */
+/* and a row of d slots at fan-out k keeps every slot when d <= k, else the  */
+/* k positions with the smallest (key, p), in ascending p.                   */
+/* Seeds are layer 0 (a repeated seed counts once); a vertex first reached   */
+/* while layer h is expanded gets layer h + 1; the vertices of layer <       */
+/* num_hops are expanded, each once. vertices[] are the visited ids          */
+/* ascending, layers[] their layer; for each expanded vertex in ascending    */
+/* id its selected slots in ascending position are emitted as (sub_src =     */
+/* the neighbour's position in vertices[], sub_dst = the vertex's) for 'in', */
+/* the other way round for 'out', parent_eid = the slot's eid; the j-th      */
+/* emitted edge is subgraph edge j. The arrays are a function of (CSR,       */
+/* seeds, num_hops, fanout, seed) alone, the same on every run and the same  */
+/* as dglhip_neighbor_sample_host gives: the atomics only decide which slot  */
+/* claims a vertex for the next frontier, whose order nothing depends on.    */
+/* The caller owns the loop: an init call, then one hop call per layer h =   */
+/* 0 .. num_hops - 1 while the frontier is not empty, each followed by one   */
+/* host read of `status` (int64[4], device memory; so none of them can run   */
+/* under stream capture), then the final call, which needs no read:          */
+/*   status[0] length of the next frontier (after the init call: of the      */
+/*             first, the distinct seeds),                                   */
+/*   status[1] seeds outside [0, num_nodes) (init call); such an id is       */
+/*             counted and never used as an index, and with any the sample   */
+/*             must not go on,                                               */
+/*   status[2] edges the rows of the frontier just expanded emit: the sum    */
+/*             of min(degree, fanout) (hop call),                            */
+/*   status[3] 0.                                                            */
+/* The subgraph has as many vertices as the frontiers hold together and as   */
+/* many edges as the hops' status[2] sum to.                                 */
+/* State between the calls: layer int32[num_nodes], set by the init call.    */
+/* A row of up to DGLHIP_SAMPLE_REG_SLOTS slots keeps its keys in registers  */
+/* during the selection; a longer one recomputes them in every pass.         */
+/* ------------------------------------------------------------------------ */
+#define DGLHIP_SAMPLE_REG_SLOTS 256
+/* The hash of the rule and the key of one slot (host). */
+uint64_t dglhip_sample_mix(uint64_t z);
+uint64_t dglhip_sample_key(uint64_t seed, int64_t vertex, int64_t position);
+/* Bytes of the final call's workspace for a sample of num_vertices vertices */
+/* (-1 on an error): the subgraph id of every node int32[num_nodes], the     */
+/* rows' edge counts and bases, the scans' storage.                          */
+int64_t dglhip_neighbor_sample_workspace_bytes(int64_t num_nodes, int64_t num_vertices);
+/* Layer zero: resets layer, validates the seeds and writes the distinct ones
+ * to frontier[0 .. status[0]) (room for num_seeds ids), in no fixed order. */
+int dglhip_neighbor_sample_init_device(int64_t num_nodes, const int64_t* seeds, int64_t num_seeds,
+                                       int32_t* layer, int64_t* frontier, int64_t* status,
+                                       void* stream);
+/* One hop: expands frontier[0 .. frontier_len), the vertices of layer `hop`,
+ * and writes the vertices it reaches first to next[0 .. status[0]) in no fixed
+ * order. next has room for next_capacity ids and nothing is written past it;
+ * min(num_nodes - vertices so far, frontier_len * fanout) is always enough. */
+int dglhip_neighbor_sample_hop_device(int64_t num_nodes, int64_t nnz, const int64_t* indptr,
+                                      const int32_t* indices, const int64_t* frontier,
+                                      int64_t frontier_len, int hop, int64_t fanout, uint64_t seed,
+                                      int32_t* layer, int64_t* next, int64_t next_capacity,
+                                      int64_t* status, void* stream);
+/* The final stage: vertices and layers (int64[num_vertices]) and sub_src,
+ * sub_dst, parent_eid (int64[num_edges]) from the layer map the hops left.
+ * num_hops, fanout and seed are those of the hop calls. No host sync. */
+int dglhip_neighbor_sample_final_device(int64_t num_nodes, int64_t nnz, const int64_t* indptr,
+                                        const int32_t* indices, const int64_t* eid,
+                                        int in_direction, int num_hops, int64_t fanout,
+                                        uint64_t seed, const int32_t* layer, int64_t num_vertices,
+                                        int64_t num_edges, int64_t* vertices, int64_t* layers,
+                                        int64_t* sub_src, int64_t* sub_dst, int64_t* parent_eid,
+                                        void* workspace, int64_t workspace_bytes, void* stream);
+/* Host twin over host arrays: computes the same sample and leaves it with the
+ * calling thread; sizes (int64[2]) = {vertices, edges}. A seed outside
+ * [0, num_nodes) returns -1 with a message. */
+int dglhip_neighbor_sample_host(int64_t num_nodes, int64_t nnz, const int64_t* indptr,
+                                const int32_t* indices, const int64_t* eid, int in_direction,
+                                const int64_t* seeds, int64_t num_seeds, int num_hops,
+                                int64_t fanout, uint64_t seed, int64_t* sizes);
+/* Copies out (and drops) the sample the last dglhip_neighbor_sample_host call
+ * of this thread left; the sizes must be the ones it reported. */
+int dglhip_neighbor_sample_host_fetch(int64_t num_vertices, int64_t num_edges, int64_t* vertices,
+                                      int64_t* layers, int64_t* sub_src, int64_t* sub_dst,
+                                      int64_t* parent_eid);
+
+/* ------------------------------------------------------------------------ */
 /* Weighted softmax cross-entropy over node rows (csrc/node_loss.hip): the   */
 /* loss of a full-graph node classifier. No reference counterpart: the       */
 /* reference's examples call torch's F.cross_entropy / nll_loss             */
