@@ -603,27 +603,40 @@ int dglhip_gspmm_chunked_device(int msg_op, int reduce_op, int64_t feat_len,
   API_END();
 }
 
-int dglhip_gspmm_items_table_device(int msg_op, int64_t num_items, int64_t feat_len,
-                                    const int32_t* item_rows, const int64_t* item_ptr,
-                                    int accumulate, const int32_t* indices, const int64_t* eid,
-                                    const float* ufeat, int64_t ufeat_ld, int64_t ufeat_rows,
-                                    int items_per_wave, const float* efeat, int64_t efeat_len,
-                                    float* out, void* stream_) {
+int dglhip_gspmm_items_columns_device(int msg_op, int64_t num_items, int64_t feat_len,
+                                      const int32_t* item_rows, const int64_t* item_ptr,
+                                      int accumulate, const int32_t* indices, const int64_t* eid,
+                                      const float* ufeat, int64_t ufeat_ld, int64_t ufeat_rows,
+                                      int items_per_wave, int column_parts, const float* efeat,
+                                      int64_t efeat_len, float* out, void* stream_) {
   API_BEGIN();
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   DGLHIP_CHECK(msg_op >= 0 && msg_op <= 3, "unknown msg op " << msg_op);
   DGLHIP_CHECK(num_items >= 0 && feat_len >= 0 && ufeat_rows >= 0, "negative size");
   DGLHIP_CHECK(items_per_wave == 1 || items_per_wave == 2,
                "items_per_wave " << items_per_wave << ": 1 or 2");
+  DGLHIP_CHECK(column_parts == 1 || column_parts == 2,
+               "column_parts " << column_parts << ": 1 or 2");
   if (num_items == 0 || feat_len == 0) return 0;
   DGLHIP_CHECK(item_rows && item_ptr && indices && out, "null items/indices/out");
   const int64_t elen = check_operands(msg_op, feat_len, ufeat, efeat, efeat_len);
   check_ufeat_ld(ufeat_ld, feat_len);
   SumLaunch a{num_items, feat_len, elen, nullptr, indices, eid, ufeat, efeat,
               out, item_rows, item_ptr, item_ptr + 1, accumulate != 0, false, ufeat_ld,
-              ufeat_rows, items_per_wave};
+              ufeat_rows, items_per_wave, items_per_wave == 2 ? column_parts : 1};
   dispatch_sum(msg_op, false, a, stream);
   API_END();
+}
+
+int dglhip_gspmm_items_table_device(int msg_op, int64_t num_items, int64_t feat_len,
+                                    const int32_t* item_rows, const int64_t* item_ptr,
+                                    int accumulate, const int32_t* indices, const int64_t* eid,
+                                    const float* ufeat, int64_t ufeat_ld, int64_t ufeat_rows,
+                                    int items_per_wave, const float* efeat, int64_t efeat_len,
+                                    float* out, void* stream_) {
+  return dglhip_gspmm_items_columns_device(msg_op, num_items, feat_len, item_rows, item_ptr,
+                                           accumulate, indices, eid, ufeat, ufeat_ld, ufeat_rows,
+                                           items_per_wave, 1, efeat, efeat_len, out, stream_);
 }
 
 int dglhip_gspmm_items_device(int msg_op, int64_t num_items, int64_t feat_len,

@@ -455,6 +455,138 @@ __global__ __launch_bounds__(256) void gspmm_items_pair_kernel(
   else if (two) store_out<4, ACCUM ? 2 : 4>(out + r1 * F, f0, acc);
 }
 
+// Lane j of every 16-lane row (a DPP row) handed to the whole row.
+__device__ __forceinline__ uint32_t row_broadcast(uint32_t v, int j) {
+  switch (j) {
+#define DGLHIP_ROW_BCAST(J) \
+  case J: return __builtin_amdgcn_update_dpp(0, v, 0x150 + J, 0xf, 0xf, true);
+    DGLHIP_ROW_BCAST(0) DGLHIP_ROW_BCAST(1) DGLHIP_ROW_BCAST(2) DGLHIP_ROW_BCAST(3)
+    DGLHIP_ROW_BCAST(4) DGLHIP_ROW_BCAST(5) DGLHIP_ROW_BCAST(6) DGLHIP_ROW_BCAST(7)
+    DGLHIP_ROW_BCAST(8) DGLHIP_ROW_BCAST(9) DGLHIP_ROW_BCAST(10) DGLHIP_ROW_BCAST(11)
+    DGLHIP_ROW_BCAST(12) DGLHIP_ROW_BCAST(13) DGLHIP_ROW_BCAST(14)
+#undef DGLHIP_ROW_BCAST
+    default: return __builtin_amdgcn_update_dpp(0, v, 0x15f, 0xf, 0xf, true);
+  }
+}
+
+// Column halves: four items per wave over one half of the columns, for the
+// launches of gspmm_items_pair_kernel (DESIGN.md §4.1 "Column halves"). A
+// workgroup gathers only columns [64 * half, 64 * half + 64) of every source
+// row, half = (block % 8) & 1: blocks b and b + 8 share an XCD, so each XCD's
+// L2 holds one half of the launch's source slice instead of all of it. The
+// label is for speed only: block b takes half b & 1 of item group b >> 1 (16
+// items), a bijection onto all the work wherever the block runs. Wave w of a
+// group takes items 4w .. 4w + 3, one per quarter (16 lanes, a DPP row, 16
+// bytes per lane), so one gather instruction still fetches 1 KiB: four half
+// rows. The column ids of a batch come from one vector load, lane 16t + j
+// reading item t's slot k + j and turning it into the row's byte offset (or,
+// past the item's end, an offset past the table, which the descriptor's
+// range check answers without a fetch); a row broadcast hands slot j's offset
+// to its quarter. The next batch's ids are loaded behind the gathers. Each
+// lane adds its item's slots in slot order from zero (ACCUM: from the running
+// row) and a switched-off lane adds nothing: the chain of gspmm_sum_kernel,
+// the same bits. Running rows as in the pair kernel, one store per quarter.
+template <int DEPTH, bool ACCUM>
+__global__ __launch_bounds__(256) void gspmm_items_columns_kernel(
+    int64_t num_items, int64_t ldu, uint32_t table_bytes,
+    const int32_t* __restrict__ indices, const float* __restrict__ ufeat,
+    float* __restrict__ out, const int32_t* __restrict__ item_rows,
+    const int64_t* __restrict__ item_ptr) {
+  static_assert(DEPTH >= 1 && DEPTH <= 16, "a batch's ids are one 16-lane row");
+  typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+  constexpr int64_t F = 128;
+  constexpr uint32_t kOff = 0xfffffc00u;  // + any lane offset: past every gated table
+  const int lane = threadIdx.x & 63;
+  const int q = lane >> 4, ql = lane & 15;
+  const int64_t bl = block_linear();
+  const int half = static_cast<int>(bl % 8) & 1;
+  const int64_t wave =
+      (bl >> 1) * (blockDim.x >> 6) +
+      __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
+  const int64_t i0 = wave * 4;
+  if (i0 >= num_items) return;
+  // quarter t: slots [p[t], p[t + 1]) into row r[t]; none past the last item
+  int64_t p[5];
+  int64_t r[4];
+#pragma unroll
+  for (int t = 0; t < 5; ++t) p[t] = item_ptr[i0 + t < num_items ? i0 + t : num_items];
+#pragma unroll
+  for (int t = 0; t < 4; ++t) r[t] = item_rows[i0 + t < num_items ? i0 + t : num_items - 1];
+  int n[4], rel[4];
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    n[t] = static_cast<int>(p[t + 1] - p[t]);
+    rel[t] = static_cast<int>(p[t] - p[0]);
+  }
+  const int nmin = min(min(n[0], n[1]), min(n[2], n[3]));
+  const int nmax = max(max(n[0], n[1]), max(n[2], n[3]));
+  const int my_n = q == 0 ? n[0] : (q == 1 ? n[1] : (q == 2 ? n[2] : n[3]));
+  const int my_rel = q == 0 ? rel[0] : (q == 1 ? rel[1] : (q == 2 ? rel[2] : rel[3]));
+  const int64_t my_row = q == 0 ? r[0] : (q == 1 ? r[1] : (q == 2 ? r[2] : r[3]));
+  const bool owns = i0 + q < num_items;
+  const int32_t* __restrict__ idx = indices + p[0];
+  const uint32_t ld4 = static_cast<uint32_t>(ldu) * 4u;
+  const uint32_t lane_off = static_cast<uint32_t>(half) * 256u + static_cast<uint32_t>(ql) * 16u;
+  const __amdgpu_buffer_rsrc_t table = __builtin_amdgcn_make_buffer_rsrc(
+      const_cast<float*>(ufeat), 0, static_cast<int>(table_bytes), 0x00020000);
+  const int64_t f0 = int64_t(half) * 64 + int64_t(ql) * 4;
+
+  // this lane's share of the batch at slot k: the byte offset of the row of
+  // slot k + ql of its quarter's item. The load stays inside the wave's slots
+  // (an ended item re-reads its last id, an empty one a neighbour's).
+  auto batch_ids = [&](int k) -> uint32_t {
+    const int s = max(min(k + ql, my_n - 1) + my_rel, 0);
+    const uint32_t id = static_cast<uint32_t>(idx[s]);
+    return k + ql < my_n ? id * ld4 : kOff;
+  };
+
+  f32x4 acc = Vec<4>::zero();
+  if (ACCUM && owns) acc = load_out<4, 2>(out + my_row * F, f0);
+  if (nmax > 0) {
+    uint32_t ids = batch_ids(0);
+    int k = 0;
+    // every item has DEPTH slots left: every lane gathers, no predicate
+#pragma unroll 1
+    for (; k + DEPTH <= nmin; k += DEPTH) {
+      u32x4 v[DEPTH];
+#pragma unroll
+      for (int j = 0; j < DEPTH; ++j)
+        v[j] = __builtin_amdgcn_raw_buffer_load_b128(table, row_broadcast(ids, j) + lane_off, 0,
+                                                     0);
+      if (k + DEPTH < nmax) ids = batch_ids(k + DEPTH);  // uniform
+#pragma unroll
+      for (int j = 0; j < DEPTH; ++j) acc += *reinterpret_cast<const f32x4*>(&v[j]);
+    }
+    // the rest as predicated batches, every gather of a batch in flight
+    // together; a lane whose item has no slot k + j gathers past the table and
+    // does not add the value (not even a zero: -0.0 + 0.0 is +0.0)
+#pragma unroll 1
+    for (; k < nmax; k += DEPTH) {
+      const int rb = nmax - k;
+      u32x4 v[DEPTH];
+#pragma unroll
+      for (int j = 0; j < DEPTH; ++j) {
+        if (j < rb)  // uniform
+          v[j] = __builtin_amdgcn_raw_buffer_load_b128(table, row_broadcast(ids, j) + lane_off,
+                                                       0, 0);
+      }
+      if (k + DEPTH < nmax) ids = batch_ids(k + DEPTH);  // uniform
+#pragma unroll
+      for (int j = 0; j < DEPTH; ++j) {
+        if (j < rb) {
+          const f32x4 sum = acc + *reinterpret_cast<const f32x4*>(&v[j]);
+          acc = k + j < my_n ? sum : acc;
+        }
+      }
+    }
+  }
+  // one store per quarter: the row of a store is uniform, as store_out's
+  // descriptor has to be
+#pragma unroll
+  for (int t = 0; t < 4; ++t)
+    if (q == t && i0 + t < num_items) store_out<4, ACCUM ? 2 : 4>(out + r[t] * F, f0, acc);
+}
+
 // Combine the chunk partials of each heavy row in chunk order:
 // out[row] = ((p0 + p1) + p2) + ... (deterministic), then MEAN scaling; with
 // ACCUM the row's running value comes first: out[row] = ((out[row] + p0) + p1) ...;
@@ -660,6 +792,7 @@ struct SumLaunch {
   int64_t ldu = 0;           // ufeat row stride in elements (0: F)
   int64_t urows = 0;         // rows of ufeat (0: not known)
   int items_per_wave = 1;    // 2: gspmm_items_pair_kernel where it applies
+  int column_parts = 1;      // 2: gspmm_items_columns_kernel where it applies
 };
 
 // Outputs past twice the 256 MiB Infinity Cache are stored non-temporally
@@ -680,6 +813,32 @@ static inline bool items_pair_applies(const SumLaunch& a) {
          reinterpret_cast<uintptr_t>(a.ufeat) % 16 == 0 &&
          reinterpret_cast<uintptr_t>(a.out) % 16 == 0 &&
          a.urows * ldu * int64_t(sizeof(float)) < (int64_t(1) << 32);
+}
+
+// Whether it takes the column-half kernel instead: the pair kernel's gate,
+// and a table that ends 1 KiB below 4 GiB (a switched-off lane's offset plus
+// its column offset must neither wrap nor fall inside the table).
+static inline bool items_columns_applies(const SumLaunch& a) {
+  const int64_t ldu = a.ldu ? a.ldu : a.F;
+  return a.column_parts == 2 && items_pair_applies(a) &&
+         a.urows * ldu * int64_t(sizeof(float)) <= int64_t(0xfffffc00u);
+}
+
+static inline void launch_items_columns(const SumLaunch& a, hipStream_t stream) {
+  // 12 gathers in flight per lane: the most that keep 64 VGPRs, so 8 waves per
+  // SIMD (8 / 10 / 12 / 14 / 16 measured: DESIGN.md §4.1 "Column halves")
+  constexpr int DEPTH = 12;
+  // 16 items (4 waves of 4) per pair of blocks, one block per column half
+  const int64_t blocks = 2 * ((a.num_items + 15) / 16);
+  DGLHIP_CHECK(blocks <= 0x7fffffff, "grid too large: " << blocks);
+  const int64_t ldu = a.ldu ? a.ldu : a.F;
+  auto kernel = a.accumulate ? gspmm_items_columns_kernel<DEPTH, true>
+                             : gspmm_items_columns_kernel<DEPTH, false>;
+  timed_launch(stream, [&] {
+    hipLaunchKernelGGL(kernel, grid_1d(blocks), dim3(256), 0, stream, a.num_items, ldu,
+                       static_cast<uint32_t>(a.urows * ldu * int64_t(sizeof(float))), a.indices,
+                       a.ufeat, a.out, a.row_order, a.chunk_beg);
+  });
 }
 
 static inline void launch_items_pair(const SumLaunch& a, hipStream_t stream) {
@@ -729,6 +888,11 @@ static inline void launch_sum(const SumLaunch& a, hipStream_t stream) {
       // 7; Reddit-shaped headline 3.74 -> 3.61 ms, same bits); the running
       // rows under RP 2, the first launch, which only stores, under RP 4.
       // With items_per_wave 2, rows of 128 floats go two items to a wave.
+      // With column_parts 2 on top, four items to a wave over a column half.
+      if (items_columns_applies(a)) {
+        launch_items_columns(a, stream);
+        return;
+      }
       if (items_pair_applies(a)) {
         launch_items_pair(a, stream);
         return;

@@ -54,6 +54,7 @@ SpmmPolicy policy_from_env() {
   p.short_rows = env_str("DGLHIP_SHORT_ROWS", "on") != "off";
   p.pad_rows = env_str("DGLHIP_PAD_ROWS", "auto") == "auto";
   p.items_per_wave = env_str("DGLHIP_ITEMS_PER_WAVE", "2") == "1" ? 1 : 2;
+  p.column_parts = env_str("DGLHIP_COLUMN_PARTS", "2") == "1" ? 1 : 2;
   return p;
 }
 
@@ -129,6 +130,8 @@ void set_spmm_policy(const SpmmPolicy& p) {
   DGLHIP_CHECK(p.row_split >= -1, "row_split: -1 auto, 0 off or a chunk length");
   DGLHIP_CHECK(p.items_per_wave == 1 || p.items_per_wave == 2,
                "items_per_wave " << p.items_per_wave << ": 1 or 2");
+  DGLHIP_CHECK(p.column_parts == 1 || p.column_parts == 2,
+               "column_parts " << p.column_parts << ": 1 or 2");
   std::lock_guard<std::mutex> lk(g_pol_mu);
   pol_ref() = p;
 }
@@ -832,6 +835,7 @@ struct Decision {
   // the value the mean is added to)
   int64_t ws_sums = 0;
   int items_per_wave = 1;  // blocked items a wave takes (gspmm_items_pair_kernel: 2)
+  int column_parts = 1;    // 2: the column halves of gspmm_items_columns_kernel
   int64_t total() const { return ws_pad + ws_vals + ws_map + ws_partial + ws_sums; }
 };
 
@@ -910,10 +914,17 @@ Decision decide(SpmmPlan& plan, const RunArgs& a, hipStream_t s) {
       // Cache, and there the pair kernel's second dependent batch (items of
       // 12-13 slots against 10 in flight) costs more than its 16-byte
       // gathers save: the emulated N = 4 rank's 12-MB slices ran 6.50 ms
-      // against the one-item kernel's 6.34.
+      // against the one-item kernel's 6.34. Over column
+      // halves an L2 sees half a slice and a batch is 12 slots, so every
+      // stretch (block_max_stretch: 3) keeps them: that rank ran 4.42 ms
+      // against 6.34, and 15- and 18-MiB slices of the headline graph 3.87
+      // and 4.26 ms against the one-item kernel's 5.44 and 5.68
+      // (profiles/r12/columns/emulated_ranks.json, depth_slice/).
       const auto lh = plan.span(s);
       const double slice = static_cast<double>(lh.second - lh.first) * ld_in * elem / d.bp->B;
-      d.items_per_wave = p.items_per_wave == 2 && slice <= 1.5 * p.block_bytes ? 2 : 1;
+      const double reach = p.column_parts == 2 ? 3.0 : 1.5;
+      d.items_per_wave = p.items_per_wave == 2 && slice <= reach * p.block_bytes ? 2 : 1;
+      d.column_parts = d.items_per_wave == 2 ? p.column_parts : 1;
       if (mean_add) d.ws_sums = align256(plan.num_rows() * a.F * 4);
       if (!strided && fp32u && pad_rows(p, a.msg, DGLHIP_REDUCE_SUM, a.F, a.urows)) {
         d.pad = true;
@@ -1061,11 +1072,11 @@ void run_planned(SpmmPlan& plan, const RunArgs& a, const Decision& d, void* work
     }
     for (size_t i = 0; i < bp.launches.size(); ++i) {
       const BlockItems& it = bp.launches[i];
-      DGLHIP_CHECK(dglhip_gspmm_items_table_device(
+      DGLHIP_CHECK(dglhip_gspmm_items_columns_device(
                        a.msg, it.n_items, a.F, it.rows.data<int32_t>(), it.ptr.data<int64_t>(),
                        (i == 0 && first_writes) ? 0 : 1, bp.indices.data<int32_t>(),
                        ev ? nullptr : erows, static_cast<const float*>(uf), d.ld, a.urows,
-                       d.items_per_wave,
+                       d.items_per_wave, d.column_parts,
                        ev ? ev : (a.msg == DGLHIP_MSG_U_MUL_E ? a.efeat : nullptr),
                        elen, sums, s) == 0,
                    DGLGetLastError());
@@ -1265,6 +1276,8 @@ int dglhip_spmm_get_policy(DGLHipSpmmPolicy* out) {
   out->block_min_row_bytes = p.block_min_row_bytes;
   out->tier_min_rows = p.tier_min_rows;
   out->pad_min_bytes = p.pad_min_bytes;
+  out->column_parts = p.column_parts;
+  out->reserved = 0;
   API_END();
 }
 
@@ -1286,6 +1299,7 @@ int dglhip_spmm_set_policy(const DGLHipSpmmPolicy* in) {
   p.block_min_row_bytes = in->block_min_row_bytes;
   p.tier_min_rows = in->tier_min_rows;
   p.pad_min_bytes = in->pad_min_bytes;
+  p.column_parts = in->column_parts;
   set_spmm_policy(p);
   API_END();
 }

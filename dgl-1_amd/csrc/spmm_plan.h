@@ -52,6 +52,7 @@ struct SpmmPolicy {
   int64_t block_min_row_bytes = 128;
   int64_t tier_min_rows = 1 << 16;
   int64_t pad_min_bytes = 4 << 20;
+  int column_parts = 2;            // blocked items over column halves (gspmm_items_columns_kernel), or 1
 };
 
 SpmmPolicy spmm_policy();

@@ -263,10 +263,11 @@ typedef struct DGLHipSpmmPlanObj* DGLHipSpmmPlan;
  * only when it is the launch's critical path), blocked 1, short_rows 1,
  * pad_rows 1, items_per_wave 2, block_bytes 6 MiB, block_table_min 16 MiB, block_table_max
  * 256 MiB, block_min_slots 12, block_max_stretch 3, block_max_suffix 1/16,
- * block_min_row_bytes 128, tier_min_rows 65536, pad_min_bytes 4 MiB; the
+ * block_min_row_bytes 128, tier_min_rows 65536, pad_min_bytes 4 MiB,
+ * column_parts 2; the
  * environment variables DGLHIP_ROW_SPLIT / _BLOCKED / _BLOCK_BYTES /
  * _BLOCK_MIN_SLOTS / _BLOCK_MAX_STRETCH / _SHORT_ROWS / _PAD_ROWS /
- * _ITEMS_PER_WAVE set the
+ * _ITEMS_PER_WAVE / _COLUMN_PARTS set the
  * initial values. Results never depend on it beyond the documented
  * tolerance of the heavy-row split (re-association of a chunked row). */
 typedef struct {
@@ -283,6 +284,8 @@ typedef struct {
   int64_t block_min_row_bytes;               /* rows of at most this keep one launch */
   int64_t tier_min_rows;                     /* short rows needed to tier */
   int64_t pad_min_bytes;                     /* tables smaller than this: no padding */
+  int32_t column_parts;   /* 2: the pair kernel's launches over column halves, one per XCD; or 1 */
+  int32_t reserved;       /* 0 */
 } DGLHipSpmmPolicy;
 int dglhip_spmm_get_policy(DGLHipSpmmPolicy* out);
 int dglhip_spmm_set_policy(const DGLHipSpmmPolicy* policy);
@@ -850,6 +853,17 @@ int dglhip_gspmm_items_table_device(int msg_op, int64_t num_items, int64_t feat_
                                     const float* ufeat, int64_t ufeat_ld, int64_t ufeat_rows,
                                     int items_per_wave, const float* efeat, int64_t efeat_len,
                                     float* out, void* stream);
+/* The same with the schedule policy's column_parts: 1, or 2, which with
+ * items_per_wave 2 runs those launches four items to a wave over one half of
+ * the columns, the half chosen by the workgroup's XCD label (block % 8), so
+ * each XCD's L2 holds half of the source slice; it also needs ufeat to end
+ * 1 KiB below 4 GiB. With items_per_wave 1 it is ignored. The same bits. */
+int dglhip_gspmm_items_columns_device(int msg_op, int64_t num_items, int64_t feat_len,
+                                      const int32_t* item_rows, const int64_t* item_ptr,
+                                      int accumulate, const int32_t* indices, const int64_t* eid,
+                                      const float* ufeat, int64_t ufeat_ld, int64_t ufeat_rows,
+                                      int items_per_wave, int column_parts, const float* efeat,
+                                      int64_t efeat_len, float* out, void* stream);
 
 /* Source-swept copy_u + sum (mean != 0: mean) of fp32 rows of feat_len = 64,
  * 128 or 256 floats over the CSR (indptr, indices), every row of out

@@ -4,10 +4,12 @@ launches), on the Reddit-shaped graph (copy_u + sum, F = 128): the earlier
 sweeps bracketed every launch, which charged schedules with more launches
 for their markers. Bits compared with the one-launch kernel. With several
 --items-per-wave values each slice runs under each of them (1: the one-item
-kernel, 2: gspmm_items_pair_kernel), interleaved in every round.
+kernel, 2: gspmm_items_pair_kernel), interleaved in every round; with several
+--column-parts values also under each of them (2: gspmm_items_columns_kernel
+where items-per-wave is 2).
 
   python tools/block_bytes_percall.py [--mib 3 4 5 6 8] [--rounds 3] [--iters 20]
-      [--items-per-wave 1 2]
+      [--items-per-wave 1 2] [--column-parts 1 2]
 """
 import argparse
 import json
@@ -28,6 +30,8 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--items-per-wave", type=int, nargs="+", default=None,
                     help="policy values to run each slice under (default: the current one)")
+    ap.add_argument("--column-parts", type=int, nargs="+", default=None,
+                    help="policy values to run each slice under (default: the current one)")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     src, dst, n = data.reddit_like(device=dev)
@@ -41,12 +45,14 @@ def main():
     ref = out.clone()
     kernel.set_blocked(old)
     ipws = args.items_per_wave or [kernel.schedule_policy()["items_per_wave"]]
+    parts = args.column_parts or [kernel.schedule_policy()["column_parts"]]
     res = {"graph": "reddit_like", "rounds": []}
     for _ in range(args.rounds):
         row = {}
         for mib in args.mib:
-            for ipw in ipws:
-                kernel.set_schedule_policy(block_bytes=int(mib * (1 << 20)), items_per_wave=ipw)
+            for ipw, cp in [(i, c) for i in ipws for c in parts if i == 2 or c == parts[0]]:
+                kernel.set_schedule_policy(block_bytes=int(mib * (1 << 20)), items_per_wave=ipw,
+                                           column_parts=cp)
                 kernel.gspmm_into(csr, out, h)
                 torch.cuda.synchronize()
                 same = bool(torch.equal(out, ref))
@@ -55,7 +61,11 @@ def main():
                     kernel.gspmm_into(csr, out, h)
                 ms, calls = kernel.timing_read()
                 kernel.timing_enable(False)
-                key = "%g" % mib if args.items_per_wave is None else "%g/ipw%d" % (mib, ipw)
+                key = "%g" % mib
+                if args.items_per_wave is not None:
+                    key += "/ipw%d" % ipw
+                if args.column_parts is not None:
+                    key += "/cp%d" % cp
                 row[key] = {"ms": ms / calls, "blocks": kernel.blocked_schedule(adj, h),
                             "bits_equal": same}
         res["rounds"].append(row)
