@@ -354,7 +354,11 @@ int dglhip_typed_block_spmm_host(int64_t num_rows, int64_t num_blocks, int64_t i
   API_BEGIN();
   DGLHIP_CHECK(num_rows >= 0 && num_blocks > 0 && in_block > 0 && out_block > 0, "bad sizes");
   if (num_rows == 0) return 0;
-  DGLHIP_CHECK(indptr && indices && slot_rel && ufeat && weight && out, "null pointer argument");
+  DGLHIP_CHECK(indptr && out, "null pointer argument");
+  // no slots (indptr[num_rows] == 0): what only a slot reads may be null, the
+  // rows are zero-filled below
+  DGLHIP_CHECK(indptr[num_rows] == 0 || (indices && slot_rel && ufeat && weight),
+               "null pointer argument");
   const int64_t nb = num_blocks, si = in_block, so = out_block;
   const int64_t Fi = nb * si, Fo = nb * so, wr = nb * si * so;
   const int nt = num_threads > 0 ? num_threads : default_num_threads();
@@ -385,7 +389,10 @@ int dglhip_typed_block_wgrad_host(int64_t num_rels, int64_t num_blocks, int64_t 
   const int64_t nb = num_blocks, si = in_block, so = out_block;
   const int64_t Fi = nb * si, Fo = nb * so, wr = nb * si * so;
   if (num_rels == 0 || wr == 0) return 0;
-  DGLHIP_CHECK(rel_ptr && ufeat && dout && dweight, "null pointer argument");
+  DGLHIP_CHECK(rel_ptr && dweight, "null pointer argument");
+  // no positions (rel_ptr[num_rels] == 0): dweight is zero-filled below
+  DGLHIP_CHECK(rel_ptr[num_rels] == 0 || (rel_src && rel_dst && ufeat && dout),
+               "null pointer argument");
   const int nt = num_threads > 0 ? num_threads : default_num_threads();
   typed_chunked_rows(num_rels, wr, rel_ptr, dweight, nt, [&](int64_t k0, int64_t k1, float* o) {
     for (int64_t k = k0; k < k1; ++k) {

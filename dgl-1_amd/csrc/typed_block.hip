@@ -838,8 +838,13 @@ int dglhip_typed_block_spmm_device(int64_t num_rows, int64_t num_items, int64_t 
                in_block > 0 && out_block > 0, "bad sizes");
   const int64_t Fo = num_blocks * out_block;
   if (num_rows == 0) return 0;
-  DGLHIP_CHECK(indptr && item_ptr && item_row && indices && slot_rel && ufeat && weight && out,
-               "null pointer argument");
+  DGLHIP_CHECK(indptr && item_ptr && item_row && out, "null pointer argument");
+  // a null array that only a slot reads says there are no slots (indptr is
+  // not read here: no host sync); nothing walks them, the rows are zeros
+  if (!indices || !slot_rel || !ufeat || !weight) {
+    HIP_CALL(hipMemsetAsync(out, 0, size_t(num_rows) * size_t(Fo) * sizeof(float), stream));
+    return 0;
+  }
   DGLHIP_CHECK(num_heavy == 0 || partial, "chunked rows need their partials");
   // outputs per lane: a wave covers up to 64 * T of them, T capped by
   // g_typed_t (the study knob dglhip_set_typed_block_width; default 1)
@@ -916,8 +921,9 @@ int dglhip_typed_block_msg_device(int64_t num_rels, int64_t num_items, int64_t n
   DGLHIP_CHECK(Fi <= 1024 && Fo <= 1024, "message rows of " << Fi << " -> " << Fo
                                                              << " features: at most 1024");
   if (num_rels == 0 || num_items == 0) return 0;
-  DGLHIP_CHECK(rel_ptr && item_ptr && item_rel && pos_row && pos_slot && ufeat && weight && msg,
-               "null pointer argument");
+  DGLHIP_CHECK(rel_ptr && item_ptr && item_rel, "null pointer argument");
+  // a null per-position array (or operand): no positions, no message to store
+  if (!pos_row || !pos_slot || !ufeat || !weight || !msg) return 0;
   DGLHIP_CHECK(num_items <= 0x7fffffff, "grid too large");
   const int Q = (Fi > 512 || Fo > 512) ? 4 : 2;
   const size_t lds = size_t(kMsgRows) * size_t(Fi) * sizeof(float);
@@ -956,7 +962,12 @@ int dglhip_typed_msg_sum_device(int64_t num_rows, int64_t num_items, int64_t fea
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   DGLHIP_CHECK(num_rows >= 0 && num_items >= 0 && num_heavy >= 0 && feat_len > 0, "bad sizes");
   if (num_rows == 0) return 0;
-  DGLHIP_CHECK(indptr && item_ptr && item_row && msg && out, "null pointer argument");
+  DGLHIP_CHECK(indptr && item_ptr && item_row && out, "null pointer argument");
+  // no message rows: no slots (as the entries above), the rows are zeros
+  if (!msg) {
+    HIP_CALL(hipMemsetAsync(out, 0, size_t(num_rows) * size_t(feat_len) * sizeof(float), stream));
+    return 0;
+  }
   DGLHIP_CHECK(num_heavy == 0 || partial, "chunked rows need their partials");
   const int64_t n64 = (feat_len + 63) / 64;
   const int T = n64 >= 8 ? 8 : (n64 >= 4 ? 4 : (n64 >= 2 ? 2 : 1));
@@ -1002,14 +1013,19 @@ int dglhip_typed_block_wgrad_scaled_device(int64_t num_rels, int64_t num_items,
                in_block >= 0 && out_block >= 0, "bad sizes");
   const int64_t wr = num_blocks * in_block * out_block;
   if (num_rels == 0 || wr == 0) return 0;
-  DGLHIP_CHECK(rel_ptr && item_ptr && item_rel && ufeat && dout && dweight,
-               "null pointer argument");
+  DGLHIP_CHECK(rel_ptr && item_ptr && item_rel && dweight, "null pointer argument");
+  // a null per-position array (or operand): no positions, every relation's
+  // gradient is zero
+  if (!rel_src || !rel_dst || !ufeat || !dout) {
+    HIP_CALL(hipMemsetAsync(dweight, 0, size_t(num_rels) * size_t(wr) * sizeof(float), stream));
+    return 0;
+  }
   DGLHIP_CHECK(num_heavy == 0 || partial, "chunked relations need their partials");
   const int64_t total = num_items * wr;
   DGLHIP_CHECK((total + 255) / 256 <= 0x7fffffff, "grid too large");
   const int64_t Fi = num_blocks * in_block, Fo = num_blocks * out_block;
   const int qw = round_up_q((wr + 255) / 256);
-  if (typed_msg_level() >= 1 && qw > 0 && Fi <= 1024 && Fo <= 1024 && rel_src && rel_dst) {
+  if (typed_msg_level() >= 1 && qw > 0 && Fi <= 1024 && Fo <= 1024) {
     // staged rows (r06): one workgroup per item
     const int R = (Fi > 512 || Fo > 512) ? 4 : 2;
     const size_t lds = size_t(kMsgRows) * size_t(Fi + Fo + 1) * sizeof(float);

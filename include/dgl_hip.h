@@ -1156,6 +1156,21 @@ int dglhip_gat_dropout_mask_host(int64_t num_slots, int64_t num_heads, float dro
 /* slots: each chunk is one sequential fma chain in slot order, and a row   */
 /* of several chunks is their partial sums added in chunk order. The host   */
 /* entry points run the same chains (identical bits).                       */
+/*                                                                          */
+/* Null pointers on empty inputs. An empty tensor's data pointer is null,   */
+/* so the arrays that only a slot (or a relation-major position) reads may  */
+/* be NULL when there are none: indices, slot_rel, slot_norm, ufeat and     */
+/* weight of the g-SpMM; pos_row, pos_slot, ufeat, weight and msg of the    */
+/* message entry, slot_map, slot_norm and msg of the sum entry; rel_src,    */
+/* rel_dst, rel_norm, ufeat and dout of the weight gradient. The row        */
+/* pointers, the item lists and the outputs are always                      */
+/* required (num_rows or num_rels == 0 returns before any pointer is looked */
+/* at). A host entry reads the slot count from indptr[num_rows] (rel_ptr    */
+/* [num_rels]) and accepts such a NULL only when it is 0. A device entry    */
+/* cannot read it without a sync: there a NULL among those arrays declares  */
+/* that there are no slots, and the entry launches nothing that walks them. */
+/* Either way every output row is written: out and dweight are zeros (no    */
+/* message is stored).                                                      */
 /* ------------------------------------------------------------------------ */
 #define DGLHIP_TYPED_CHUNK 64
 /* Device form: the chunks as items. item_ptr[num_rows+1] = each row's first

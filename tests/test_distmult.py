@@ -138,6 +138,10 @@ def test_distmult_link_loss_matches_float64(device, F):
     dev = _dev(device)
     h, w, s, r, o = _case(F=F, N=900)  # rows past 700 see no triple
     s, o = s % 700, o % 700
+    _check_link_loss(dev, h, w, s, r, o)
+
+
+def _check_link_loss(dev, h, w, s, r, o):
     labels = (torch.arange(s.numel()) % 2).float()
     reg = 0.01
     h1, w1 = h.clone().to(dev).requires_grad_(True), w.clone().to(dev).requires_grad_(True)
@@ -164,3 +168,130 @@ def test_distmult_link_loss_matches_float64(device, F):
     for got, want, bound in ((h1.grad, h2.grad, ha.grad), (w1.grad, w2.grad, wa.grad)):
         err = (got.double().cpu() - want).abs()
         assert bool((err <= 1e-5 * bound + 1e-30).all()), float((err / (bound + 1e-30)).max())
+
+
+# ---- widths and sample counts at the kernels' cuts -------------------------
+# F: T = 1 up to 64 features per wave slice, T = 2 at 65..128, T = 4 at
+# 193..448, T = 8 beyond, two passes past 512; a last slice with idle lanes at
+# 63, 129 and 513. Samples: the score and loss kernels take 4 per workgroup, so
+# 1, 2, 3, 5 and 261 leave a last workgroup with idle waves.
+EDGE_F = [1, 63, 65, 128, 129, 300, 448, 512, 513, 1000]
+EDGE_N = [1, 2, 3, 5, 261]
+EDGE_NODES, EDGE_RELS = 40, 6
+
+
+def _edge_triples(n):
+    """(s, r, o) over 40 nodes and 6 relations, relation 0 never used. At 261
+    samples the positions sit at the 64-position chunk: node 1 is the subject
+    of exactly 64 samples, node 2 of 65, node 3 the object of 128 (none of
+    them on the other side, so their gradient rows hold exactly that many
+    positions), and relation 1 holds 129 samples."""
+    rng = np.random.default_rng(100 + n)
+    if n == 261:
+        s = np.concatenate([np.full(64, 1), np.full(65, 2), rng.integers(4, EDGE_NODES, 132)])
+        o = np.concatenate([np.full(128, 3), rng.integers(4, EDGE_NODES, 133)])
+        r = np.concatenate([np.full(129, 1), rng.integers(2, EDGE_RELS, 132)])
+        s, o, r = rng.permutation(s), rng.permutation(o), rng.permutation(r)
+    else:
+        s, o = rng.integers(0, EDGE_NODES, n), rng.integers(0, EDGE_NODES, n)
+        r = rng.integers(1, EDGE_RELS, n)
+    return tuple(torch.from_numpy(a.astype(np.int64)) for a in (s, r, o))
+
+
+def test_edge_triples_have_the_intended_counts():
+    s, r, o = _edge_triples(261)
+    assert s.numel() == r.numel() == o.numel() == 261
+    subj, obj = torch.bincount(s, minlength=EDGE_NODES), torch.bincount(o, minlength=EDGE_NODES)
+    assert subj[1] == 64 and subj[2] == 65 and obj[3] == 128
+    # their rows of dh hold exactly those positions of cat(s, o): 1, 2 and 3 chunks' edges
+    both = subj + obj
+    assert both[1] == 64 and both[2] == 65 and both[3] == 128
+    assert torch.bincount(r, minlength=EDGE_RELS)[1] == 129
+    ptr_, _ = kernel._position_groups(torch.cat([s, o]), EDGE_NODES)
+    item_ptr, _ = kernel._typed_items(ptr_, 522)
+    assert (item_ptr[1:] - item_ptr[:-1])[:4].tolist() == [1, 1, 2, 2]
+    for n in EDGE_N:
+        s, r, o = _edge_triples(n)
+        assert s.numel() == n and int(r.min()) >= 1  # relation 0 is never used
+        assert int(s.max()) < EDGE_NODES and int(o.max()) < EDGE_NODES and int(r.max()) < EDGE_RELS
+
+
+def _edge_case(F, n):
+    gen = torch.Generator().manual_seed(7 * F + n)
+    h = torch.randn(EDGE_NODES, F, generator=gen)
+    w = torch.randn(EDGE_RELS, F, generator=gen)
+    dsc = torch.randn(n, generator=gen)
+    return (h, w) + _edge_triples(n) + (dsc,)
+
+
+def _edge_run(F, n, dev):
+    h, w, s, r, o, dsc = (t.to(dev) for t in _edge_case(F, n))
+    h1, w1 = h.clone().requires_grad_(True), w.clone().requires_grad_(True)
+    for t in (h, w):  # NaNs where the allocator is about to hand memory out again
+        del_me = torch.full_like(t, float("nan"))
+        del del_me
+    sc = kernel.distmult_score(h1, w1, s, r, o)
+    g = torch.autograd.grad(sc, (h1, w1), dsc)
+    return sc.detach(), g[0], g[1]
+
+
+@pytest.mark.parametrize("device", DEVICES)
+@pytest.mark.parametrize("F", EDGE_F)
+def test_distmult_widths_and_partial_blocks(device, F):
+    """Every width class of distmult_grad_kernel<T> (one pass and two) and
+    sample counts that leave idle waves and idle batch slots: gradients with
+    the bits of the gather_rows torch form, scores within 1e-6 * Σ|terms| of
+    float64, and an exactly zero gradient row for the unused relation."""
+    dev = _dev(device)
+    for n in EDGE_N:
+        h, w, s, r, o, dsc = (t.to(dev) for t in _edge_case(F, n))
+        sc, dh, dw = _edge_run(F, n, dev)
+        h2, w2 = h.clone().requires_grad_(True), w.clone().requires_grad_(True)
+        ref = _torch_form(h2, w2, s, r, o)
+        g2 = torch.autograd.grad(ref, (h2, w2), dsc)
+        assert torch.equal(dh, g2[0]) and torch.equal(dw, g2[1])
+        terms = h.double()[s] * w.double()[r] * h.double()[o]
+        exact, mag = terms.sum(1), terms.abs().sum(1)
+        err = (sc.double() - exact).abs()
+        print(F, n, device, "worst score err / bound = %.3g" % float((err / (1e-6 * mag + 1e-30)).max()))
+        assert (err <= 1e-6 * mag + 1e-30).all()
+        assert (dw[0].view(torch.int32) == 0).all()
+        untouched = torch.ones(EDGE_NODES, dtype=torch.bool)
+        untouched[torch.cat([s, o]).cpu()] = False
+        assert not dh.cpu()[untouched].any()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("F", EDGE_F)
+def test_distmult_widths_host_equals_device(F):
+    dev = _dev("cuda")
+    for n in EDGE_N:
+        for a, b in zip(_edge_run(F, n, torch.device("cpu")), _edge_run(F, n, dev)):
+            assert torch.equal(a.view(torch.int32), b.cpu().view(torch.int32))
+
+
+@pytest.mark.parametrize("device", DEVICES)
+@pytest.mark.parametrize("n", [1, 3])
+@pytest.mark.parametrize("F", [37, 513])
+def test_distmult_link_loss_partial_blocks(device, F, n):
+    """distmult_link_loss at 1 and 3 samples: a last (only) workgroup with
+    idle waves, and with 40 x F and 6 x F elements over 512 h^2 / w^2 chunks,
+    chunks that are empty. The bounds of test_distmult_link_loss_matches_float64."""
+    dev = _dev(device)
+    h, w, s, r, o, _ = _edge_case(F, n)
+    _check_link_loss(dev, h, w, s, r, o)
+
+
+@pytest.mark.gpu
+def test_position_groups_items_of_no_ids():
+    """kernel._position_groups_items over an empty id tensor (a null data
+    pointer) equals the host build: every row empty, one item per row."""
+    _dev("cuda")
+    ids = torch.empty(0, dtype=torch.int64)
+    for rows in (1, EDGE_RELS, 70):
+        ph, oh = kernel._position_groups(ids, rows)
+        pd, od, ipd, ird = kernel._position_groups_items(ids.cuda(), rows)
+        assert torch.equal(ph, pd.cpu()) and torch.equal(oh, od.cpu()) and od.numel() == 0
+        iph, irh = kernel._typed_items(ph, 0)
+        assert torch.equal(iph, ipd.cpu()) and torch.equal(irh, ird.cpu())
+        assert iph.tolist() == list(range(rows + 1))

@@ -87,6 +87,40 @@ def test_relgraphconv(device):
     torch.testing.assert_close(out, ref, rtol=1e-4, atol=1e-5)
 
 
+@pytest.mark.parametrize("device", DEVICES)
+def test_relgraphconv_isolated_nodes(device):
+    """Five nodes and no edge: every node gets what the layer gives a node
+    without in-edges — the self-loop product and the bias, the aggregate
+    being exact zeros — with and without the 1 / in-degree norm, and backward
+    runs: a zero relation-weight gradient (a tensor, not None). The same
+    module on the host gives the same values."""
+    dev = _dev(device)
+    g = dgl.DGLGraph(multigraph=True)
+    g.add_nodes(5)
+    torch.manual_seed(0)
+    host = dglnn.RelGraphConv(8, 6, num_rels=4, num_bases=2)
+    with torch.no_grad():
+        host.bias.copy_(torch.randn(6))
+    conv = dglnn.RelGraphConv(8, 6, num_rels=4, num_bases=2).to(dev)
+    conv.load_state_dict(host.state_dict())
+    x = torch.randn(5, 8)
+    et = torch.empty(0, dtype=torch.int64)
+    for norm in (None, torch.ones(5, 1)):
+        xd = x.clone().to(dev).requires_grad_(True)
+        conv.zero_grad()
+        out = conv(g, xd, et.to(dev), None if norm is None else norm.to(dev))
+        assert out.shape == (5, 6)
+        want = x @ host.loop_weight + host.bias  # + an aggregate of zeros
+        torch.testing.assert_close(out.detach().cpu(), want.detach(), rtol=1e-4, atol=1e-5)
+        torch.testing.assert_close(out.detach().cpu(), host(g, x, et, norm).detach(),
+                                   rtol=1e-4, atol=1e-5)
+        out.backward(torch.ones_like(out))
+        assert conv.weight.grad is not None and conv.weight.grad.shape == conv.weight.shape
+        assert not conv.weight.grad.any()
+        torch.testing.assert_close(xd.grad.cpu(), (torch.ones(5, 6) @ host.loop_weight.t()).detach(),
+                                   rtol=1e-4, atol=1e-5)
+
+
 def test_node_linear_matches_linear():
     """NodeLinear == nn.Linear: same forward bits, gradients within fp32
     summation tolerance (split-K weight gradient, chunked bias gradient), on a
