@@ -21,6 +21,7 @@ from .batched_graph import (BatchedDGLGraph, batch, unbatch, split,  # noqa: F40
 from .subgraph import DGLSubGraph  # noqa: F401
 from .traversal import *  # noqa: F401,F403
 from .propagate import *  # noqa: F401,F403
+from .transform import *  # noqa: F401,F403
 from .udf import EdgeBatch, NodeBatch  # noqa: F401
 from .runtime import ir  # noqa: F401
 from . import nn  # noqa: F401

@@ -537,6 +537,18 @@ class DGLGraph(object):
         sgi = self._graph.edge_subgraph(utils.toindex(edges))
         return DGLSubGraph(self, sgi.induced_nodes, sgi.induced_edges, sgi)
 
+    # -- transforms (graph.py:2786-2798) ------------------------------------------
+    def line_graph(self, backtracking=True, shared=False, ctx=None):
+        """The line graph of this graph: see :func:`dgl.transform.line_graph`."""
+        from .transform import line_graph
+        return line_graph(self, backtracking, shared, ctx)
+
+    def reverse(self, share_ndata=False, share_edata=False):
+        """This graph with every edge turned round: see
+        :func:`dgl.transform.reverse`."""
+        from .transform import reverse
+        return reverse(self, share_ndata, share_edata)
+
     def filter_nodes(self, predicate, nodes=ALL):
         """Ids of the nodes that satisfy ``predicate``, a function of a
         :class:`~dgl.udf.NodeBatch` returning a 1-D boolean mask. The ids are

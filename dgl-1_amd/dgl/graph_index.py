@@ -312,6 +312,43 @@ class GraphIndex(object):
         nid = v.detach().to(torch.int64).reshape(-1)
         return SubgraphIndex(self, nid, eid, device_coo=(nid.numel(), src, dst))
 
+    # -- line graph (graph_index.py:793-808) -------------------------------------
+    def line_graph(self, backtracking=True):
+        """The line graph of a mutable index (``_CAPI_DGLGraphLineGraph``): one
+        node per edge; edge ``i = (u, v)`` links to the out-edges of ``v`` in
+        edge-id order, without those back to ``u`` unless ``backtracking``. A
+        plain mutable, non-multigraph index."""
+        if self._readonly:
+            raise DGLError("line_graph isn't implemented in immutable graph")
+        h = _call("_CAPI_DGLGraphLineGraph", self._h(), int(bool(backtracking)))
+        return GraphIndex(False, False, handle=h)
+
+    def line_graph_device(self, ctx, backtracking=True):
+        """:meth:`line_graph` built on the ROCm device ``ctx`` from the
+        source-major CSR of the cached adjacency (kernel.line_graph): the same
+        edges in the same order, left on the device. The returned index builds
+        its native graph only when a query or a mutation needs it."""
+        if self._readonly:
+            raise DGLError("line_graph isn't implemented in immutable graph")
+        if torch.cuda.is_current_stream_capturing():  # before anything is launched
+            raise DGLError("line_graph() on a device reads the line graph's size on the host: "
+                           "it cannot run while a stream is being captured")
+        ctx = torch.device(ctx)
+        if ctx.type != "cuda":
+            raise DGLError("line_graph_device needs a ROCm device, got %s" % (ctx,))
+        if ctx.index is None:
+            ctx = torch.device("cuda", torch.cuda.current_device())
+        adj = self.adjacency(ctx)
+        coo = getattr(self, "_dev_coo", None)
+        if coo is not None and coo[0].device == ctx:
+            src, dst = coo  # this index already lives there
+        else:
+            src, dst, _ = self._id_order()
+            both = torch.stack([src, dst]).to(ctx)  # one upload
+            src, dst = both[0], both[1]
+        lsrc, ldst = kernel.line_graph(adj.bwd, src, dst, backtracking)
+        return _DeviceLineGraphIndex(self._m, lsrc, ldst)
+
     # -- neighbour sampling (graph_index.py:664-678, 1018-1027) ------------------
     def neighbor_sampling(self, seed_ids, expand_factor, num_hops, neighbor_type, node_prob,
                           seed=None):
@@ -459,7 +496,76 @@ class GraphIndex(object):
         g._handle = None  # ownership moved to self
 
 
-class SubgraphIndex(GraphIndex):
+class _DeviceCOOIndex(GraphIndex):
+    """An index whose edge list a device kernel left on the GPU as
+    ``_dev_coo = (src, dst)`` in edge-id order, with the sizes known from the
+    construction: the g-SpMM CSRs on that device come straight from the device
+    arrays, and the native index is only built, from one download of the edge
+    list, when a query needs it (:attr:`has_native_index`). With ``_dev_coo``
+    None it behaves as the plain index around ``_handle``."""
+
+    _dev_coo = None
+
+    def _h(self):
+        if self._handle is None:
+            # the extraction validated the endpoints: straight into a new index
+            src, dst = (t.cpu() for t in self._dev_coo)
+            if self._readonly:
+                # a sampled subgraph of a read-only parent: an immutable index
+                # whose edge ids are the positions in the edge list
+                self._handle = _call("_CAPI_DGLGraphCreate", src, dst,
+                                     torch.arange(self._m, dtype=torch.int64),
+                                     int(self._multigraph), self._n, 1)
+                return ("handle", self._handle)
+            h = _call("_CAPI_DGLGraphCreateMutable", int(self._multigraph))
+            self._handle = h
+            _call("_CAPI_DGLGraphAddVertices", ("handle", h), self._n)
+            if self._m:
+                _call("_CAPI_DGLGraphAddEdges", ("handle", h), src, dst)
+        return ("handle", self._handle)
+
+    @property
+    def has_native_index(self):
+        """Whether the library's graph object exists yet. False for an index
+        made on the device until a structural query (``edges()``, degrees,
+        ``in_edges`` ...) asks for it; message passing over the whole graph
+        on that device never does. Read-only."""
+        return self._handle is not None
+
+    def _on_coo_device(self, ctx):
+        if self._dev_coo is None or ctx.type != "cuda":
+            return False
+        idx = ctx.index if ctx.index is not None else torch.cuda.current_device()
+        return self._dev_coo[0].device == torch.device("cuda", idx)
+
+    def adjacency(self, ctx):
+        ctx = torch.device(ctx)
+        if not self._on_coo_device(ctx):
+            return super(_DeviceCOOIndex, self).adjacency(ctx)
+        ctx = self._dev_coo[0].device
+        key = ("adj", str(ctx))
+        if key not in self._cache:
+            src, dst = self._dev_coo
+            # (slots in the order the index itself would give: edge ids under a
+            # mutable parent, (dst, src) under a read-only one)
+            self._cache[key] = kernel.from_coo(self._n, self._n, dst, src, self._slot_order(),
+                                               ctx, validate=False)
+        return self._cache[key]
+
+    def incidence_in(self, ctx):
+        ctx = torch.device(ctx)
+        if not self._on_coo_device(ctx):
+            return super(_DeviceCOOIndex, self).incidence_in(ctx)
+        key = ("inc_in", str(ctx))
+        if key not in self._cache:
+            dst = self._dev_coo[1]
+            eids = torch.arange(self._m, dtype=torch.int64, device=dst.device)
+            self._cache[key] = kernel.from_coo(self._n, self._m, dst, eids, kernel.ORDER_EID,
+                                               dst.device, validate=False)
+        return self._cache[key]
+
+
+class SubgraphIndex(_DeviceCOOIndex):
     """The index of a subgraph (graph_index.py:810-890): a read-only structure
     that remembers which parent nodes and edges it was induced from.
 
@@ -490,32 +596,6 @@ class SubgraphIndex(GraphIndex):
             self._n, self._m = int(n), int(src.numel())
             self._dev_coo = (src, dst)
 
-    def _h(self):
-        if self._handle is None:
-            # the extraction validated the endpoints: straight into a new index
-            src, dst = (t.cpu() for t in self._dev_coo)
-            if self._readonly:
-                # a sampled subgraph of a read-only parent: an immutable index
-                # whose edge ids are the positions in the edge list
-                self._handle = _call("_CAPI_DGLGraphCreate", src, dst,
-                                     torch.arange(self._m, dtype=torch.int64),
-                                     int(self._multigraph), self._n, 1)
-                return ("handle", self._handle)
-            h = _call("_CAPI_DGLGraphCreateMutable", int(self._multigraph))
-            self._handle = h
-            _call("_CAPI_DGLGraphAddVertices", ("handle", h), self._n)
-            if self._m:
-                _call("_CAPI_DGLGraphAddEdges", ("handle", h), src, dst)
-        return ("handle", self._handle)
-
-    @property
-    def has_native_index(self):
-        """Whether the library's graph object exists yet. False for a subgraph
-        extracted on the device until a structural query (``edges()``,
-        degrees, ``in_edges`` ...) asks for it; message passing over the whole
-        subgraph on that device never does. Read-only."""
-        return self._handle is not None
-
     @property
     def induced_nodes(self):
         """int64 parent id of every subgraph node (on the device for a device
@@ -526,38 +606,6 @@ class SubgraphIndex(GraphIndex):
     def induced_edges(self):
         """int64 parent id of every subgraph edge."""
         return self._induced_edges
-
-    def _on_coo_device(self, ctx):
-        if self._dev_coo is None or ctx.type != "cuda":
-            return False
-        idx = ctx.index if ctx.index is not None else torch.cuda.current_device()
-        return self._dev_coo[0].device == torch.device("cuda", idx)
-
-    def adjacency(self, ctx):
-        ctx = torch.device(ctx)
-        if not self._on_coo_device(ctx):
-            return super(SubgraphIndex, self).adjacency(ctx)
-        ctx = self._dev_coo[0].device
-        key = ("adj", str(ctx))
-        if key not in self._cache:
-            src, dst = self._dev_coo
-            # (slots in the order the index itself would give: edge ids under a
-            # mutable parent, (dst, src) under a read-only one)
-            self._cache[key] = kernel.from_coo(self._n, self._n, dst, src, self._slot_order(),
-                                               ctx, validate=False)
-        return self._cache[key]
-
-    def incidence_in(self, ctx):
-        ctx = torch.device(ctx)
-        if not self._on_coo_device(ctx):
-            return super(SubgraphIndex, self).incidence_in(ctx)
-        key = ("inc_in", str(ctx))
-        if key not in self._cache:
-            dst = self._dev_coo[1]
-            eids = torch.arange(self._m, dtype=torch.int64, device=dst.device)
-            self._cache[key] = kernel.from_coo(self._n, self._m, dst, eids, kernel.ORDER_EID,
-                                               dst.device, validate=False)
-        return self._cache[key]
 
     def add_nodes(self, num):
         raise DGLError("Readonly graph. Mutation is not allowed.")
@@ -573,6 +621,39 @@ class SubgraphIndex(GraphIndex):
 
     def __setstate__(self, state):
         raise NotImplementedError("SubgraphIndex unpickling is not supported yet.")
+
+
+class _DeviceLineGraphIndex(_DeviceCOOIndex):
+    """The mutable, non-multigraph index of a line graph whose edge list
+    GraphIndex.line_graph_device left on the GPU. The first mutation builds
+    the native index, drops the device edge list and the caches, and goes on
+    as any index does."""
+
+    def __init__(self, n, src, dst):
+        # not GraphIndex.__init__: that creates a native index at once
+        self._handle = None
+        self._multigraph = False
+        self._readonly = False
+        self._cache = {}
+        self._n, self._m = int(n), int(src.numel())
+        self._dev_coo = (src, dst)
+
+    def _leave_device(self):
+        self._h()
+        self._dev_coo = None
+        self._invalidate()
+
+    def add_nodes(self, num):
+        self._leave_device()
+        super(_DeviceLineGraphIndex, self).add_nodes(num)
+
+    def add_edges(self, u, v):
+        self._leave_device()
+        super(_DeviceLineGraphIndex, self).add_edges(u, v)
+
+    def clear(self):
+        self._leave_device()
+        super(_DeviceLineGraphIndex, self).clear()
 
 
 def map_to_subgraph_nid(subgraph_index, parent_nids):

@@ -2796,6 +2796,81 @@ def induced_subgraph(csr, sel):
 
 
 # ---------------------------------------------------------------------------
+# Line graph on the device (csrc/line_graph.hip)
+# ---------------------------------------------------------------------------
+LINE_GRAPH_TILE = 256  # DGLHIP_LINE_GRAPH_TILE: candidates per work unit
+
+
+def line_graph_count(csr_bwd, src, dst, backtracking):
+    """Stage A of :func:`line_graph`: (workspace, [line-graph edges M,
+    candidates K, invalid endpoints, work units]), the four counts read once
+    through pinned memory."""
+    dev = csr_bwd.device
+    N, E = csr_bwd.num_rows, src.numel()
+    nbytes = LIB.dglhip_line_graph_workspace_bytes(N, E)
+    if nbytes < 0:
+        check_call(-1)
+    ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
+    status = torch.empty(4, dtype=torch.int64, device=dev)
+    check_call(LIB.dglhip_line_graph_count_device(
+        N, E, ptr(src) if E else None, ptr(dst) if E else None, ptr(csr_bwd.indptr),
+        ptr(csr_bwd.indices) if E else None, int(bool(backtracking)), ptr(ws), int(nbytes),
+        ptr(status), _stream_of(dev)))
+    host = torch.empty(4, dtype=torch.int64, pin_memory=True)
+    host.copy_(status, non_blocking=True)
+    torch.cuda.current_stream(dev).synchronize()
+    return ws, host.tolist()
+
+
+def line_graph_fill(csr_bwd, src, dst, backtracking, ws, units, m):
+    """Stage B: (lsrc, ldst), int64[m] each, on the device."""
+    dev = csr_bwd.device
+    out = torch.empty(2, m, dtype=torch.int64, device=dev)
+    if m:
+        check_call(LIB.dglhip_line_graph_fill_device(
+            csr_bwd.num_rows, src.numel(), ptr(src), ptr(dst), ptr(csr_bwd.indptr),
+            ptr(csr_bwd.indices), ptr(csr_bwd.eid), int(bool(backtracking)), ptr(ws),
+            ws.numel(), int(units), int(m), ptr(out[0]), ptr(out[1]), _stream_of(dev)))
+    return out[0], out[1]
+
+
+def line_graph(csr_bwd, src, dst, backtracking):
+    """The edge list of the line graph of a graph, from its endpoints ``src``,
+    ``dst`` in edge-id order (int64, on the device of ``csr_bwd``) and its
+    source-major CSR in edge-id order (``SparseAdj.bwd`` of an ORDER_EID
+    adjacency): ``(lsrc, ldst)`` in the order of the native index's
+    line_graph (for edge i = (u, v), the out-edges of v in edge-id order,
+    without those back to u unless ``backtracking``).
+
+    One host read per call (the edge count and the validation counter), so it
+    cannot run while the current stream is being captured. An endpoint
+    outside the graph raises DGLError, and so does a line graph whose edge
+    list would not fit in the device's free memory: its size is quadratic in
+    the degree of a hub."""
+    dev = csr_bwd.device
+    if dev.type != "cuda":
+        raise DGLError("the device route of line_graph() needs a CSR on a ROCm device")
+    if torch.cuda.is_current_stream_capturing():
+        raise DGLError("line_graph() on a device reads the line graph's size on the host: "
+                       "it cannot run while a stream is being captured")
+    src = src.detach().to(device=dev, dtype=torch.int64).reshape(-1).contiguous()
+    dst = dst.detach().to(device=dev, dtype=torch.int64).reshape(-1).contiguous()
+    if src.numel() != dst.numel() or src.numel() != csr_bwd.nnz:
+        raise DGLError("line_graph(): %d sources, %d destinations and a CSR of %d edges"
+                       % (src.numel(), dst.numel(), csr_bwd.nnz))
+    ws, (m, _, invalid, units) = line_graph_count(csr_bwd, src, dst, backtracking)
+    if invalid:
+        raise DGLError("Invalid vertex: %d endpoints of the %d edges are not in a graph of %d "
+                       "nodes" % (invalid, src.numel(), csr_bwd.num_rows))
+    need = 16 * m
+    free = torch.cuda.mem_get_info(dev)[0]
+    if need > free:
+        raise DGLError("the line graph has M = %d edges: its edge list needs %d bytes and the "
+                       "device has %d free" % (m, need, free))
+    return line_graph_fill(csr_bwd, src, dst, backtracking, ws, units, m)
+
+
+# ---------------------------------------------------------------------------
 # BFS and topological frontiers on the device (csrc/traversal.hip)
 # ---------------------------------------------------------------------------
 TRAVERSAL_CHUNK = 512  # DGLHIP_TRAVERSAL_CHUNK: slots per item of a level's walk

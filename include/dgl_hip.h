@@ -530,6 +530,51 @@ int dglhip_induced_subgraph_fill_device(int64_t num_nodes, int64_t num_selected,
                                         int64_t* sub_dst, int64_t* parent_eid, void* stream);
 
 /* ------------------------------------------------------------------------ */
+/* Line graph on the device (csrc/line_graph.hip): the reference's           */
+/* GraphOp::LineGraph (src/graph/graph_op.cc:17-31) of a graph whose edge    */
+/* list and source-major CSR are already on the device: src, dst             */
+/* int64[num_edges] in edge-id order; indptr int64[num_nodes + 1], indices   */
+/* int32[num_edges] (the destinations), eid int64[num_edges]; row u holds    */
+/* the out-edges of u in edge-id order (DGLHIP_ORDER_EID).                   */
+/* For i = 0..num_edges-1 the out-edges of dst[i] in slot order are emitted  */
+/* as (lsrc = i, ldst = the slot's eid), except, when `backtracking` is 0,   */
+/* those whose destination is src[i]; the k-th emitted pair is line-graph    */
+/* edge k: the arrays of the native index's line_graph, element for element, */
+/* the same on every run (positions come from two scans and wave ballots,    */
+/* not from atomics).                                                        */
+/* The candidates are the concatenation over i of the slots of row dst[i];   */
+/* DGLHIP_LINE_GRAPH_TILE consecutive candidates are one work unit.          */
+/* Two calls share one workspace, with one host read of `status` between     */
+/* them (so neither can run under stream capture):                           */
+/*   status[0] edges M of the line graph, status[1] candidates K (M = K with */
+/*   backtracking), status[2] endpoints of src / dst outside [0, num_nodes), */
+/*   status[3] work units, ceil(K / DGLHIP_LINE_GRAPH_TILE).                 */
+/* An edge with an invalid endpoint is counted and never followed; with      */
+/* status[2] non-zero the other entries describe the graph without those     */
+/* edges. indptr values are clamped into [0, num_edges]. num_nodes and       */
+/* num_edges must be below 2^31.                                             */
+/* ------------------------------------------------------------------------ */
+#define DGLHIP_LINE_GRAPH_TILE 256
+/* Bytes of the workspace the two calls share (-1 on an error). */
+int64_t dglhip_line_graph_workspace_bytes(int64_t num_nodes, int64_t num_edges);
+/* Stage A: validation, candidate offsets, and without backtracking the
+ * survivors per wave and their scan; fills status (int64[4], device memory).
+ * No host sync inside. */
+int dglhip_line_graph_count_device(int64_t num_nodes, int64_t num_edges, const int64_t* src,
+                                   const int64_t* dst, const int64_t* indptr,
+                                   const int32_t* indices, int backtracking, void* workspace,
+                                   int64_t workspace_bytes, int64_t* status, void* stream);
+/* Stage B: writes the num_line_edges = status[0] entries of lsrc and ldst
+ * (int64 each) from the workspace stage A left, walking the num_units =
+ * status[3] units. Same sizes, arrays and `backtracking` as stage A. */
+int dglhip_line_graph_fill_device(int64_t num_nodes, int64_t num_edges, const int64_t* src,
+                                  const int64_t* dst, const int64_t* indptr,
+                                  const int32_t* indices, const int64_t* eid, int backtracking,
+                                  void* workspace, int64_t workspace_bytes, int64_t num_units,
+                                  int64_t num_line_edges, int64_t* lsrc, int64_t* ldst,
+                                  void* stream);
+
+/* ------------------------------------------------------------------------ */
 /* BFS and topological frontiers on the device (csrc/traversal.hip): the     */
 /* reference's BFSNodes / BFSEdges / TopologicalNodes                        */
 /* (src/graph/traversal.h) over a CSR that is already on the device: indptr  */
