@@ -16,14 +16,9 @@
 
 #include "../../include/dgl_hip.h"
 #include "common.h"
+#include "timing.h"
 
 namespace dglhip {
-
-#define HIP_CALL(expr)                                                        \
-  do {                                                                        \
-    hipError_t _e = (expr);                                                   \
-    DGLHIP_CHECK(_e == hipSuccess, #expr << " -> " << hipGetErrorString(_e)); \
-  } while (0)
 
 namespace {
 

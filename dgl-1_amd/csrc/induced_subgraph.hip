@@ -15,8 +15,8 @@
 //      is not live lost the scatter to a duplicate and is counted. A live
 //      position contributes ceil(deg / C) items of at most C =
 //      DGLHIP_SUBGRAPH_CHUNK slots; the item counts are scanned (rocPRIM) and
-//      every item finds its position by a binary search, as the typed-block
-//      item list does (typed_block.hip).
+//      every item finds its position by the shared item-row search
+//      (compact.h).
 //   3. one wave per item counts the slots whose destination is selected; the
 //      counts are scanned in item order, which is (position, chunk) order.
 //   status = {edges, invalid ids, duplicate positions, items}.
@@ -32,12 +32,7 @@
 // probes of newid are the random part, and four strides of indices are loaded
 // before their four probes so that a wave keeps four probes in flight.
 #include "../../include/dgl_hip.h"
-#include "common.h"
-#include "launch.h"
-#include "timing.h"
-
-#include <hip/hip_runtime.h>
-#include <rocprim/device/device_scan.hpp>
+#include "compact.h"
 
 namespace dglhip {
 
@@ -50,21 +45,11 @@ constexpr int kUnroll = 4;  // strides whose probes are in flight together
 
 static_assert(kChunk % (64 * kUnroll) == 0, "a chunk is a whole number of unrolled strides");
 
-int64_t round256(int64_t v) { return (v + 255) & ~int64_t(255); }
-
 // Items of a selection of n positions over a CSR of nnz slots: the live
 // positions are distinct rows, so their ceil(deg / C) sum to at most
 // min(n, N) + nnz / C.
 int64_t item_bound(int64_t N, int64_t n, int64_t nnz) {
   return (n < N ? n : N) + nnz / kChunk + 1;
-}
-
-size_t scan_bytes(int64_t len) {
-  size_t bytes = 0;
-  HIP_CALL(rocprim::inclusive_scan(nullptr, bytes, static_cast<const int64_t*>(nullptr),
-                                   static_cast<int64_t*>(nullptr), size_t(len),
-                                   rocprim::plus<int64_t>()));
-  return bytes;
 }
 
 // The workspace both stages share (all sections 256-byte aligned).
@@ -73,17 +58,17 @@ struct Layout {
   int64_t newid, nit, item_ptr, item_row, item_cnt, item_base, scan, scan_len, total;
   Layout(int64_t N, int64_t n, int64_t nnz) {
     bound = item_bound(N, n, nnz);
-    int64_t o = 0;
-    newid = o; o += round256(N * 4);
-    nit = o; o += round256(n * 8);
-    item_ptr = o; o += round256((n + 1) * 8);
-    item_row = o; o += round256(bound * 4);
-    item_cnt = o; o += round256(bound * 8);
-    item_base = o; o += round256((bound + 1) * 8);
-    scan = o;
-    const size_t s0 = n > 0 ? scan_bytes(n) : 0, s1 = scan_bytes(bound);
+    Carve c;
+    newid = c.take(N * 4);
+    nit = c.take(n * 8);
+    item_ptr = c.take((n + 1) * 8);
+    item_row = c.take(bound * 4);
+    item_cnt = c.take(bound * 8);
+    item_base = c.take((bound + 1) * 8);
+    const size_t s0 = n > 0 ? scan_bytes_i64(n) : 0, s1 = scan_bytes_i64(bound);
     scan_len = round256(int64_t(s0 > s1 ? s0 : s1));
-    total = o + scan_len;
+    scan = c.take(scan_len);
+    total = c.off;
   }
 };
 
@@ -105,13 +90,6 @@ struct Args {
   int64_t* parent_eid;
 };
 
-__device__ __forceinline__ void wave_count(bool hit, int64_t* counter) {
-  const unsigned long long mask = __ballot(hit);
-  if (mask != 0 && (threadIdx.x & 63) == 0)
-    atomicAdd(reinterpret_cast<unsigned long long*>(counter),
-              static_cast<unsigned long long>(__popcll(mask)));
-}
-
 __global__ __launch_bounds__(kThreads) void sub_scatter_kernel(Args a) {
   const int64_t i = block_linear() * kThreads + threadIdx.x;
   bool bad = false;
@@ -131,9 +109,8 @@ __global__ __launch_bounds__(kThreads) void sub_nitems_kernel(Args a) {
     int64_t items = 0;
     if (v >= 0 && v < a.N) {
       if (a.newid[v] == static_cast<int32_t>(i)) {
-        int64_t beg = a.indptr[v], end = a.indptr[v + 1];
-        beg = beg < 0 ? 0 : (beg > a.nnz ? a.nnz : beg);
-        end = end < beg ? beg : (end > a.nnz ? a.nnz : end);
+        int64_t beg, end;
+        row_range(a.indptr, a.nnz, v, &beg, &end);
         items = (end - beg + kChunk - 1) / kChunk;
       } else {
         dup = true;
@@ -142,21 +119,6 @@ __global__ __launch_bounds__(kThreads) void sub_nitems_kernel(Args a) {
     a.nit[i] = items;
   }
   wave_count(dup, a.status + 2);
-}
-
-// item j belongs to the position i with item_ptr[i] <= j < item_ptr[i + 1]
-// (positions without items share their successor's start and are skipped by
-// taking the last such i); n for the items past the end
-__global__ __launch_bounds__(kThreads) void sub_item_rows_kernel(Args a) {
-  const int64_t j = block_linear() * kThreads + threadIdx.x;
-  if (j >= a.bound) return;
-  int64_t lo = 0, hi = a.n;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi + 1) >> 1;
-    if (a.item_ptr[mid] <= j) lo = mid;
-    else hi = mid - 1;
-  }
-  a.item_row[j] = static_cast<int32_t>(lo);
 }
 
 // The slots [beg, end) of item j and its position; false for an item past the
@@ -168,15 +130,10 @@ __device__ __forceinline__ bool item_range(const Args& a, int64_t j, int64_t* po
   const int64_t c = j - a.item_ptr[i];
   const int64_t v = a.sel[i];
   if (c < 0 || v < 0 || v >= a.N) return false;
-  int64_t rb = a.indptr[v], re = a.indptr[v + 1];
-  rb = rb < 0 ? 0 : (rb > a.nnz ? a.nnz : rb);
-  re = re < rb ? rb : (re > a.nnz ? a.nnz : re);
-  const int64_t b = rb + c * kChunk;
-  if (b >= re) return false;
+  int64_t rb, re;
+  row_range(a.indptr, a.nnz, v, &rb, &re);
   *pos = i;
-  *beg = b;
-  *end = b + kChunk < re ? b + kChunk : re;
-  return true;
+  return item_slots(rb, re, c, kChunk, beg, end);
 }
 
 // FILL = false: item_cnt[j] = survivors of item j (0 past the end).
@@ -193,7 +150,7 @@ __global__ __launch_bounds__(kThreads) void sub_walk_kernel(Args a) {
     return;
   }
   int64_t out = FILL ? a.item_base[j] : 0;
-  const unsigned long long below = (1ull << lane) - 1ull;
+  const unsigned long long below = lanes_below(lane);
   for (int64_t s = beg; s < end; s += 64 * kUnroll) {
     int32_t d[kUnroll], p[kUnroll];
 #pragma unroll
@@ -281,16 +238,13 @@ int dglhip_induced_subgraph_count_device(int64_t num_nodes, int64_t num_selected
   API_BEGIN();
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   check_sizes(num_nodes, num_selected, nnz);
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  HIP_CALL(hipStreamIsCapturing(stream, &cap));
-  DGLHIP_CHECK(cap == hipStreamCaptureStatusNone,
-               "the induced subgraph reads its size on the host and cannot be captured");
+  check_not_capturing(stream,
+                      "the induced subgraph reads its size on the host and cannot be captured");
   DGLHIP_CHECK(status && workspace && indptr && (nnz == 0 || indices) &&
                    (num_selected == 0 || selected),
                "null pointer argument");
   const Layout L(num_nodes, num_selected, nnz);
-  DGLHIP_CHECK(workspace_bytes >= L.total, "workspace of " << workspace_bytes << " B, "
-                                                           << L.total << " needed");
+  check_workspace(workspace_bytes, L.total);
   const Args a = bind(L, num_nodes, num_selected, nnz, indptr, indices, nullptr, selected,
                       workspace, status);
   const int64_t n = num_selected;
@@ -300,25 +254,18 @@ int dglhip_induced_subgraph_count_device(int64_t num_nodes, int64_t num_selected
   if (num_nodes > 0)
     HIP_CALL(hipMemsetAsync(a.newid, 0xFF, size_t(num_nodes) * sizeof(int32_t), stream));
   char* scan_ws = static_cast<char*>(workspace) + L.scan;
-  size_t scan_len = size_t(L.scan_len);
   if (n > 0) {
     const dim3 grid = grid_1d((n + kThreads - 1) / kThreads);
     hipLaunchKernelGGL(sub_scatter_kernel, grid, dim3(kThreads), 0, stream, a);
     hipLaunchKernelGGL(sub_nitems_kernel, grid, dim3(kThreads), 0, stream, a);
     HIP_CALL(hipGetLastError());
-    HIP_CALL(rocprim::inclusive_scan(scan_ws, scan_len, static_cast<const int64_t*>(a.nit),
-                                     a.item_ptr + 1, size_t(n), rocprim::plus<int64_t>(),
-                                     stream));
+    scan_i64(scan_ws, L.scan_len, a.nit, a.item_ptr + 1, n, stream);
   }
-  hipLaunchKernelGGL(sub_item_rows_kernel, grid_1d((L.bound + kThreads - 1) / kThreads),
-                     dim3(kThreads), 0, stream, a);
+  launch_item_rows(n, L.bound, a.item_ptr, a.item_row, stream);
   hipLaunchKernelGGL((sub_walk_kernel<false>), grid_1d((L.bound + kWaves - 1) / kWaves),
                      dim3(kThreads), 0, stream, a);
   HIP_CALL(hipGetLastError());
-  scan_len = size_t(L.scan_len);
-  HIP_CALL(rocprim::inclusive_scan(scan_ws, scan_len, static_cast<const int64_t*>(a.item_cnt),
-                                   a.item_base + 1, size_t(L.bound), rocprim::plus<int64_t>(),
-                                   stream));
+  scan_i64(scan_ws, L.scan_len, a.item_cnt, a.item_base + 1, L.bound, stream);
   hipLaunchKernelGGL(sub_status_kernel, dim3(1), dim3(1), 0, stream, a);
   HIP_CALL(hipGetLastError());
   API_END();
@@ -339,8 +286,7 @@ int dglhip_induced_subgraph_fill_device(int64_t num_nodes, int64_t num_selected,
                    parent_eid,
                "null pointer argument");
   const Layout L(num_nodes, num_selected, nnz);
-  DGLHIP_CHECK(workspace_bytes >= L.total, "workspace of " << workspace_bytes << " B, "
-                                                           << L.total << " needed");
+  check_workspace(workspace_bytes, L.total);
   DGLHIP_CHECK(num_items >= 1 && num_items <= L.bound, "bad item count " << num_items);
   Args a = bind(L, num_nodes, num_selected, nnz, indptr, indices, eid, selected, workspace,
                 nullptr);

@@ -36,12 +36,7 @@
 // written exactly once, a stride's stores go to consecutive addresses, and
 // two runs give the same arrays.
 #include "../../include/dgl_hip.h"
-#include "common.h"
-#include "launch.h"
-#include "timing.h"
-
-#include <hip/hip_runtime.h>
-#include <rocprim/device/device_scan.hpp>
+#include "compact.h"
 
 namespace dglhip {
 
@@ -55,21 +50,11 @@ constexpr int64_t kMaxSegments = 8192;    // 256 CUs x 32 resident waves
 
 static_assert(kTile % 64 == 0 && kUnroll >= 1 && kUnroll <= 8, "a unit is a few whole strides");
 
-int64_t round256(int64_t v) { return (v + 255) & ~int64_t(255); }
-
 // Waves the walk is dealt to: K <= E * E, so a small graph launches no more
 // waves than it can have units.
 int64_t segments(int64_t E) {
   const int64_t units = E * E / kTile + 1;  // E < 2^31
   return units < kMaxSegments ? units : kMaxSegments;
-}
-
-size_t scan_bytes(int64_t len) {
-  size_t bytes = 0;
-  HIP_CALL(rocprim::inclusive_scan(nullptr, bytes, static_cast<const int64_t*>(nullptr),
-                                   static_cast<int64_t*>(nullptr), size_t(len),
-                                   rocprim::plus<int64_t>()));
-  return bytes;
 }
 
 // The workspace both stages share (all sections 256-byte aligned).
@@ -78,15 +63,15 @@ struct Layout {
   int64_t deg, cand_ptr, seg_cnt, seg_base, scan, scan_len, total;
   Layout(int64_t E) {
     segs = segments(E);
-    int64_t o = 0;
-    deg = o; o += round256(E * 8);
-    cand_ptr = o; o += round256((E + 1) * 8);
-    seg_cnt = o; o += round256(segs * 8);
-    seg_base = o; o += round256((segs + 1) * 8);
-    scan = o;
-    const size_t s0 = E > 0 ? scan_bytes(E) : 0, s1 = scan_bytes(segs);
+    Carve c;
+    deg = c.take(E * 8);
+    cand_ptr = c.take((E + 1) * 8);
+    seg_cnt = c.take(segs * 8);
+    seg_base = c.take((segs + 1) * 8);
+    const size_t s0 = E > 0 ? scan_bytes_i64(E) : 0, s1 = scan_bytes_i64(segs);
     scan_len = round256(int64_t(s0 > s1 ? s0 : s1));
-    total = o + scan_len;
+    scan = c.take(scan_len);
+    total = c.off;
   }
 };
 
@@ -106,20 +91,10 @@ struct Args {
   int64_t* ldst;
 };
 
-__device__ __forceinline__ void wave_count(int64_t n, int64_t* counter) {
-  // (a validation counter, not a position)
-  for (int off = 32; off > 0; off >>= 1) n += __shfl_down(n, off);
-  if (n != 0 && (threadIdx.x & 63) == 0)
-    atomicAdd(reinterpret_cast<unsigned long long*>(counter), static_cast<unsigned long long>(n));
-}
-
-// The slots [beg, end) of row v, clamped into [0, E]; v is in [0, N).
+// The slots of row v of the graph's own CSR (its nnz is E). The walk reads E
+// through the argument struct here: its code is then the measured one.
 __device__ __forceinline__ void row_range(const Args& a, int64_t v, int64_t* beg, int64_t* end) {
-  int64_t rb = a.indptr[v], re = a.indptr[v + 1];
-  rb = rb < 0 ? 0 : (rb > a.E ? a.E : rb);
-  re = re < rb ? rb : (re > a.E ? a.E : re);
-  *beg = rb;
-  *end = re;
+  dglhip::row_range(a.indptr, a.E, v, beg, end);
 }
 
 // deg[i] = outdeg(dst[i]); an edge with an endpoint outside [0, N) is counted
@@ -139,20 +114,7 @@ __global__ __launch_bounds__(kThreads) void lg_degree_kernel(Args a) {
     }
     a.deg[i] = d;
   }
-  wave_count(bad, a.status + 2);
-}
-
-// The last i in [lo, hi] with cand_ptr[i] <= k (cand_ptr[lo] <= k is given):
-// the edge that owns candidate k; edges without candidates share their
-// successor's start and are skipped by taking the last.
-__device__ __forceinline__ int64_t owner(const int64_t* cand_ptr, int64_t k, int64_t lo,
-                                         int64_t hi) {
-  while (lo < hi) {
-    const int64_t mid = (lo + hi + 1) >> 1;
-    if (cand_ptr[mid] <= k) lo = mid;
-    else hi = mid - 1;
-  }
-  return lo;
+  wave_add(bad, a.status + 2);  // a validation counter, not a position
 }
 
 // BT: backtracking (every candidate is emitted, at its own index).
@@ -170,13 +132,15 @@ __global__ __launch_bounds__(kThreads) void lg_walk_kernel(Args a) {
   const int64_t ub = w * per;
   const int64_t ue = ub + per < units ? ub + per : units;
   int64_t out = (FILL && !BT) ? a.seg_base[w] : 0;
-  const unsigned long long below = (1ull << lane) - 1ull;
+  const unsigned long long below = lanes_below(lane);
   for (int64_t unit = ub; unit < ue; ++unit) {
     const int64_t k0 = unit * kTile;
     const int64_t kend = k0 + kTile < K ? k0 + kTile : K;
-    // wave-uniform: the edges of the unit's first and last candidate
-    const int64_t first = owner(a.cand_ptr, k0, 0, a.E - 1);
-    const int64_t last = owner(a.cand_ptr, kend - 1, first, a.E - 1);
+    // wave-uniform: the edges that own the unit's first and last candidate
+    // (edges without candidates share their successor's start and are skipped
+    // by taking the last)
+    const int64_t first = last_le(a.cand_ptr, k0, 0, a.E - 1);
+    const int64_t last = last_le(a.cand_ptr, kend - 1, first, a.E - 1);
     int64_t lo[kUnroll], hi[kUnroll];
 #pragma unroll
     for (int u = 0; u < kUnroll; ++u) {
@@ -301,38 +265,28 @@ int dglhip_line_graph_count_device(int64_t num_nodes, int64_t num_edges, const i
   API_BEGIN();
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   check_sizes(num_nodes, num_edges);
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  HIP_CALL(hipStreamIsCapturing(stream, &cap));
-  DGLHIP_CHECK(cap == hipStreamCaptureStatusNone,
-               "the line graph reads its size on the host and cannot be captured");
+  check_not_capturing(stream, "the line graph reads its size on the host and cannot be captured");
   const int64_t E = num_edges;
   DGLHIP_CHECK(status && workspace && indptr && (E == 0 || (src && dst && indices)),
                "null pointer argument");
   const Layout L(E);
-  DGLHIP_CHECK(workspace_bytes >= L.total, "workspace of " << workspace_bytes << " B, "
-                                                           << L.total << " needed");
+  check_workspace(workspace_bytes, L.total);
   const Args a = bind(L, num_nodes, E, src, dst, indptr, indices, nullptr, workspace, status);
   HIP_CALL(hipMemsetAsync(status, 0, 4 * sizeof(int64_t), stream));
   HIP_CALL(hipMemsetAsync(a.cand_ptr, 0, sizeof(int64_t), stream));
   HIP_CALL(hipMemsetAsync(a.seg_base, 0, sizeof(int64_t), stream));
   char* scan_ws = static_cast<char*>(workspace) + L.scan;
-  size_t scan_len = size_t(L.scan_len);
   if (E > 0) {
     hipLaunchKernelGGL(lg_degree_kernel, grid_1d((E + kThreads - 1) / kThreads), dim3(kThreads),
                        0, stream, a);
     HIP_CALL(hipGetLastError());
-    HIP_CALL(rocprim::inclusive_scan(scan_ws, scan_len, static_cast<const int64_t*>(a.deg),
-                                     a.cand_ptr + 1, size_t(E), rocprim::plus<int64_t>(),
-                                     stream));
+    scan_i64(scan_ws, L.scan_len, a.deg, a.cand_ptr + 1, E, stream);
   }
   if (!backtracking) {
     hipLaunchKernelGGL((lg_walk_kernel<false, false>), grid_1d((L.segs + kWaves - 1) / kWaves),
                        dim3(kThreads), 0, stream, a);
     HIP_CALL(hipGetLastError());
-    scan_len = size_t(L.scan_len);
-    HIP_CALL(rocprim::inclusive_scan(scan_ws, scan_len, static_cast<const int64_t*>(a.seg_cnt),
-                                     a.seg_base + 1, size_t(L.segs), rocprim::plus<int64_t>(),
-                                     stream));
+    scan_i64(scan_ws, L.scan_len, a.seg_cnt, a.seg_base + 1, L.segs, stream);
   }
   hipLaunchKernelGGL(lg_status_kernel, dim3(1), dim3(1), 0, stream, a, backtracking ? 1 : 0);
   HIP_CALL(hipGetLastError());
@@ -357,8 +311,7 @@ int dglhip_line_graph_fill_device(int64_t num_nodes, int64_t num_edges, const in
   DGLHIP_CHECK(workspace && src && dst && indptr && indices && eid && lsrc && ldst,
                "null pointer argument");
   const Layout L(num_edges);
-  DGLHIP_CHECK(workspace_bytes >= L.total, "workspace of " << workspace_bytes << " B, "
-                                                           << L.total << " needed");
+  check_workspace(workspace_bytes, L.total);
   Args a = bind(L, num_nodes, num_edges, src, dst, indptr, indices, eid, workspace, nullptr);
   a.m = num_line_edges;
   a.lsrc = lsrc; a.ldst = ldst;

@@ -46,13 +46,9 @@
 // row is too long. Only the selected slots' indices and eid are read: the key
 // depends on the position, not on the neighbour.
 #include "../../include/dgl_hip.h"
-#include "common.h"
-#include "launch.h"
+#include "compact.h"
 #include "sample_key.h"
-#include "timing.h"
 
-#include <hip/hip_runtime.h>
-#include <rocprim/device/device_scan.hpp>
 #include <rocprim/iterator/transform_iterator.hpp>
 
 namespace dglhip {
@@ -69,21 +65,11 @@ static_assert(kRegSlots % 64 == 0 && kRegKeys >= 1 && kRegKeys <= 8,
 
 using u64 = unsigned long long;
 
-int64_t round256(int64_t v) { return (v + 255) & ~int64_t(255); }
-
 struct IsVisited {
   __host__ __device__ int32_t operator()(int32_t layer) const { return layer >= 0 ? 1 : 0; }
 };
 
 using VisitedIter = rocprim::transform_iterator<const int32_t*, IsVisited, int32_t>;
-
-size_t scan_bytes_i64(int64_t len) {
-  size_t bytes = 0;
-  HIP_CALL(rocprim::inclusive_scan(nullptr, bytes, static_cast<const int64_t*>(nullptr),
-                                   static_cast<int64_t*>(nullptr), size_t(len),
-                                   rocprim::plus<int64_t>()));
-  return bytes;
-}
 
 size_t scan_bytes_visited(int64_t len) {
   size_t bytes = 0;
@@ -98,33 +84,16 @@ size_t scan_bytes_visited(int64_t len) {
 struct Layout {
   int64_t pos, cnt, base, scan, scan_len, total;
   Layout(int64_t N, int64_t V) {
-    int64_t o = 0;
-    pos = o; o += round256(N * 4);
-    cnt = o; o += round256(V * 8);
-    base = o; o += round256((V + 1) * 8);
-    scan = o;
+    Carve c;
+    pos = c.take(N * 4);
+    cnt = c.take(V * 8);
+    base = c.take((V + 1) * 8);
     const size_t s0 = N > 0 ? scan_bytes_visited(N) : 0, s1 = V > 0 ? scan_bytes_i64(V) : 0;
     scan_len = round256(int64_t(s0 > s1 ? s0 : s1));
-    total = o + scan_len;
+    scan = c.take(scan_len);
+    total = c.off;
   }
 };
-
-// Slots [*beg, *end) of row v (v in [0, N)), clamped to the index arrays.
-__device__ __forceinline__ void row_range(const int64_t* indptr, int64_t nnz, int64_t v,
-                                          int64_t* beg, int64_t* end) {
-  int64_t b = indptr[v], e = indptr[v + 1];
-  b = b < 0 ? 0 : (b > nnz ? nnz : b);
-  e = e < b ? b : (e > nnz ? nnz : e);
-  *beg = b;
-  *end = e;
-}
-
-// The sum of c over the wave, in every lane.
-__device__ __forceinline__ int64_t wave_sum(int64_t c) {
-  long long v = c;
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
 
 // The k-th smallest (1-based, 1 <= k < d) of the d keys of a row in *thresh,
 // and how many of the keys equal to it are taken in *take_eq. Every lane of the
@@ -181,7 +150,7 @@ __device__ __forceinline__ void for_selected(uint64_t rb, int64_t d, int64_t k, 
   uint64_t thresh;
   int64_t take_eq;
   select_threshold(rb, d, k, lane, &thresh, &take_eq);
-  const u64 below = (u64(1) << lane) - 1;
+  const u64 below = lanes_below(lane);
   int64_t out = 0, eq_seen = 0;
   for (int64_t s = 0; s < d && out < k; s += 64) {
     const int64_t p = s + lane;
@@ -207,7 +176,7 @@ __device__ __forceinline__ void wave_append(bool win, int64_t id, int64_t* count
     base = static_cast<long long>(
         atomicAdd(reinterpret_cast<u64*>(count), static_cast<u64>(__popcll(mask))));
   base = __shfl(base, 0, 64);
-  const int64_t pos = base + __popcll(mask & ((u64(1) << lane) - 1));
+  const int64_t pos = base + __popcll(mask & lanes_below(lane));
   if (win && pos < cap) next[pos] = id;
 }
 
@@ -223,9 +192,7 @@ __global__ __launch_bounds__(kThreads) void ns_seed_kernel(int64_t N, int64_t n,
     if (v < 0 || v >= N) bad = true;  // counted, never used as an index
     else win = atomicCAS(layer + v, -1, 0) == -1;
   }
-  const u64 bad_mask = __ballot(bad);
-  if (bad_mask != 0 && lane == 0)
-    atomicAdd(reinterpret_cast<u64*>(status + 1), static_cast<u64>(__popcll(bad_mask)));
+  wave_count(bad, status + 1);
   wave_append(win, v, status, front, n, lane);
 }
 
@@ -327,13 +294,8 @@ void check_sizes(int64_t N, int64_t nnz) {
   DGLHIP_CHECK(N < (int64_t(1) << 31), "node ids are 32-bit in the layer map");
 }
 
-void check_not_capturing(hipStream_t stream) {
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  HIP_CALL(hipStreamIsCapturing(stream, &cap));
-  DGLHIP_CHECK(cap == hipStreamCaptureStatusNone,
-               "neighbour sampling reads every frontier's size on the host and cannot be "
-               "captured");
-}
+constexpr const char* kNoCapture =
+    "neighbour sampling reads every frontier's size on the host and cannot be captured";
 
 }  // namespace
 
@@ -361,7 +323,7 @@ int dglhip_neighbor_sample_init_device(int64_t num_nodes, const int64_t* seeds, 
   API_BEGIN();
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   check_sizes(num_nodes, 0);
-  check_not_capturing(stream);
+  check_not_capturing(stream, kNoCapture);
   DGLHIP_CHECK(num_seeds >= 0 && num_seeds < (int64_t(1) << 31),
                "bad number of seeds " << num_seeds);
   DGLHIP_CHECK(status && (num_nodes == 0 || layer) && (num_seeds == 0 || (seeds && frontier)),
@@ -386,7 +348,7 @@ int dglhip_neighbor_sample_hop_device(int64_t num_nodes, int64_t nnz, const int6
   API_BEGIN();
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   check_sizes(num_nodes, nnz);
-  check_not_capturing(stream);
+  check_not_capturing(stream, kNoCapture);
   DGLHIP_CHECK(num_nodes >= 1 && frontier_len >= 1 && frontier_len <= num_nodes && hop >= 0 &&
                    hop < (1 << 30) && fanout >= 0 && next_capacity >= 0,
                "bad hop " << hop << ": " << frontier_len << " rows, fan-out " << fanout);
@@ -423,8 +385,7 @@ int dglhip_neighbor_sample_final_device(int64_t num_nodes, int64_t nnz, const in
   DGLHIP_CHECK(num_edges == 0 || (indices && eid && sub_src && sub_dst && parent_eid),
                "null pointer argument");
   const Layout L(num_nodes, num_vertices);
-  DGLHIP_CHECK(workspace_bytes >= L.total, "workspace of " << workspace_bytes << " B, "
-                                                           << L.total << " needed");
+  check_workspace(workspace_bytes, L.total);
   char* ws = static_cast<char*>(workspace);
   FinalArgs a;
   a.N = num_nodes; a.nnz = nnz; a.V = num_vertices; a.m = num_edges; a.k = fanout;
@@ -448,10 +409,7 @@ int dglhip_neighbor_sample_final_device(int64_t num_nodes, int64_t nnz, const in
                      dim3(kThreads), 0, stream, a);
   HIP_CALL(hipGetLastError());
   if (num_edges > 0) {
-    scan_len = size_t(L.scan_len);
-    HIP_CALL(rocprim::inclusive_scan(ws + L.scan, scan_len, static_cast<const int64_t*>(a.cnt),
-                                     a.base + 1, size_t(num_vertices), rocprim::plus<int64_t>(),
-                                     stream));
+    scan_i64(ws + L.scan, L.scan_len, a.cnt, a.base + 1, num_vertices, stream);
     hipLaunchKernelGGL(ns_fill_kernel, grid_1d((num_vertices + kWaves - 1) / kWaves),
                        dim3(kThreads), 0, stream, a);
     HIP_CALL(hipGetLastError());

@@ -18,7 +18,7 @@
 //      is after the previous level's last read of `visited` and before this
 //      level's first. Both are scanned (rocPRIM): cand_ptr[i] is the candidate
 //      index of row i's first slot, item_ptr[i] its first item. Every item
-//      finds its row by a binary search, as the induced-subgraph items do.
+//      finds its row by the shared item-row search (compact.h).
 //   2. claim, one wave per item, lane k reads slot base + k. BFS: an unvisited
 //      target v gets atomicMin(claim[v], c). Topological: remain[v] is
 //      decremented and atomicMax(claim[v], key_base + c), where key_base is
@@ -39,14 +39,9 @@
 //
 // Mapping: one wave per item, four items per 256-lane workgroup; index loads
 // are whole 256-byte runs and the probes of visited / remain / claim are the
-// random part, four strides of them in flight per wave (induced_subgraph.hip).
+// random part, four strides of them in flight per wave.
 #include "../../include/dgl_hip.h"
-#include "common.h"
-#include "launch.h"
-#include "timing.h"
-
-#include <hip/hip_runtime.h>
-#include <rocprim/device/device_scan.hpp>
+#include "compact.h"
 
 namespace dglhip {
 
@@ -63,16 +58,6 @@ using u64 = unsigned long long;
 
 static_assert(kChunk % (64 * kUnroll) == 0, "a chunk is a whole number of unrolled strides");
 
-int64_t round256(int64_t v) { return (v + 255) & ~int64_t(255); }
-
-size_t scan_bytes(int64_t len) {
-  size_t bytes = 0;
-  HIP_CALL(rocprim::inclusive_scan(nullptr, bytes, static_cast<const int64_t*>(nullptr),
-                                   static_cast<int64_t*>(nullptr), size_t(len),
-                                   rocprim::plus<int64_t>()));
-  return bytes;
-}
-
 // Items of a frontier of f rows holding C slots: sum of ceil(deg / K) <= f + C / K.
 int64_t item_bound(int64_t f, int64_t C) { return f + C / kChunk + 1; }
 
@@ -82,18 +67,18 @@ struct Layout {
   int64_t deg, nit, cand_ptr, item_ptr, item_row, item_cnt, item_base, scan, scan_len, total;
   Layout(int64_t f, int64_t C) {
     bound = item_bound(f, C);
-    int64_t o = 0;
-    deg = o; o += round256(f * 8);
-    nit = o; o += round256(f * 8);
-    cand_ptr = o; o += round256((f + 1) * 8);
-    item_ptr = o; o += round256((f + 1) * 8);
-    item_row = o; o += round256(bound * 4);
-    item_cnt = o; o += round256(bound * 8);
-    item_base = o; o += round256((bound + 1) * 8);
-    scan = o;
-    const size_t s0 = scan_bytes(f), s1 = scan_bytes(bound);
+    Carve c;
+    deg = c.take(f * 8);
+    nit = c.take(f * 8);
+    cand_ptr = c.take((f + 1) * 8);
+    item_ptr = c.take((f + 1) * 8);
+    item_row = c.take(bound * 4);
+    item_cnt = c.take(bound * 8);
+    item_base = c.take((bound + 1) * 8);
+    const size_t s0 = scan_bytes_i64(f), s1 = scan_bytes_i64(bound);
     scan_len = round256(int64_t(s0 > s1 ? s0 : s1));
-    total = o + scan_len;
+    scan = c.take(scan_len);
+    total = c.off;
   }
 };
 
@@ -117,31 +102,6 @@ struct Args {
   int64_t* next_edge;
   int64_t* status;
 };
-
-__device__ __forceinline__ void wave_count(bool hit, int64_t* counter) {
-  const u64 mask = __ballot(hit);
-  if (mask != 0 && (threadIdx.x & 63) == 0)
-    atomicAdd(reinterpret_cast<u64*>(counter), static_cast<u64>(__popcll(mask)));
-}
-
-// Sum over the wave (every lane calls it), added to *counter by lane 0. An
-// integer sum: the same whatever the order of the adds.
-__device__ __forceinline__ void wave_add(int64_t x, int64_t* counter) {
-  long long v = x;
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  if ((threadIdx.x & 63) == 0 && v != 0)
-    atomicAdd(reinterpret_cast<u64*>(counter), static_cast<u64>(v));
-}
-
-// Slots [*beg, *end) of row v (v in [0, N)), clamped to the index arrays.
-__device__ __forceinline__ void row_range(const int64_t* indptr, int64_t nnz, int64_t v,
-                                          int64_t* beg, int64_t* end) {
-  int64_t b = indptr[v], e = indptr[v + 1];
-  b = b < 0 ? 0 : (b > nnz ? nnz : b);
-  e = e < b ? b : (e > nnz ? nnz : e);
-  *beg = b;
-  *end = e;
-}
 
 // Source validation and the first candidate total: status = {n, sum of the
 // in-range sources' degrees, ids outside [0, N)}.
@@ -195,21 +155,6 @@ __global__ __launch_bounds__(kThreads) void trv_degree_kernel(Args a) {
   wave_count(bad, a.status + 2);
 }
 
-// item j belongs to the row i with item_ptr[i] <= j < item_ptr[i + 1] (rows
-// without items share their successor's start and are skipped by taking the
-// last such i); f for the items past the end
-__global__ __launch_bounds__(kThreads) void trv_item_rows_kernel(Args a) {
-  const int64_t j = block_linear() * kThreads + threadIdx.x;
-  if (j >= a.bound) return;
-  int64_t lo = 0, hi = a.f;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi + 1) >> 1;
-    if (a.item_ptr[mid] <= j) lo = mid;
-    else hi = mid - 1;
-  }
-  a.item_row[j] = static_cast<int32_t>(lo);
-}
-
 // The slots [beg, end) of item j and the candidate index of slot beg; false
 // for an item past the end.
 __device__ __forceinline__ bool item_range(const Args& a, int64_t j, int64_t* beg, int64_t* end,
@@ -221,10 +166,7 @@ __device__ __forceinline__ bool item_range(const Args& a, int64_t j, int64_t* be
   if (c < 0 || v < 0 || v >= a.N) return false;
   int64_t rb, re;
   row_range(a.indptr, a.nnz, v, &rb, &re);
-  const int64_t b = rb + c * kChunk;
-  if (b >= re) return false;
-  *beg = b;
-  *end = b + kChunk < re ? b + kChunk : re;
+  if (!item_slots(rb, re, c, kChunk, beg, end)) return false;
   *cand = a.cand_ptr[i] + c * kChunk;
   return true;
 }
@@ -278,7 +220,7 @@ __global__ __launch_bounds__(kThreads) void trv_walk_kernel(Args a) {
   }
   int64_t out = FILL ? a.item_base[j] : 0;
   int64_t next_deg = 0;
-  const u64 below = (u64(1) << lane) - 1;
+  const u64 below = lanes_below(lane);
   for (int64_t s = beg; s < end; s += 64 * kUnroll) {
     int32_t d[kUnroll];
     bool ok[kUnroll], free_[kUnroll];
@@ -360,7 +302,7 @@ __global__ __launch_bounds__(kThreads) void topo_place_kernel(TopoArgs t) {
   const u64 mask = __ballot(zero);
   int64_t deg = 0;
   if (zero) {
-    const int64_t pos = t.wave_base[i >> 6] + __popcll(mask & ((u64(1) << lane) - 1));
+    const int64_t pos = t.wave_base[i >> 6] + __popcll(mask & lanes_below(lane));
     if (pos < t.N) t.out[pos] = i;
     int64_t b, e;
     row_range(t.indptr, t.nnz, i, &b, &e);
@@ -375,12 +317,12 @@ struct TopoLayout {
   int64_t waves, wave_cnt, wave_base, scan, scan_len, total;
   explicit TopoLayout(int64_t N) {
     waves = (N + 63) / 64;
-    int64_t o = 0;
-    wave_cnt = o; o += round256(waves * 8);
-    wave_base = o; o += round256((waves + 1) * 8);
-    scan = o;
-    scan_len = round256(int64_t(waves > 0 ? scan_bytes(waves) : 0));
-    total = o + scan_len;
+    Carve c;
+    wave_cnt = c.take(waves * 8);
+    wave_base = c.take((waves + 1) * 8);
+    scan_len = round256(int64_t(waves > 0 ? scan_bytes_i64(waves) : 0));
+    scan = c.take(scan_len);
+    total = c.off;
   }
 };
 
@@ -389,38 +331,24 @@ void check_graph(int64_t N, int64_t nnz) {
   DGLHIP_CHECK(N < (int64_t(1) << 31), "node ids are 32-bit in the CSR");
 }
 
-void check_not_capturing(hipStream_t stream) {
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  HIP_CALL(hipStreamIsCapturing(stream, &cap));
-  DGLHIP_CHECK(cap == hipStreamCaptureStatusNone,
-               "a traversal reads every frontier's size on the host and cannot be captured");
-}
+constexpr const char* kNoCapture =
+    "a traversal reads every frontier's size on the host and cannot be captured";
 
 template <int MODE>
 void launch_level(const Args& a, const Layout& L, char* ws, hipStream_t stream) {
   hipLaunchKernelGGL(trv_reset_kernel, dim3(1), dim3(64), 0, stream, a);
   char* scan_ws = ws + L.scan;
-  size_t scan_len = size_t(L.scan_len);
   hipLaunchKernelGGL(trv_degree_kernel, grid_1d((a.f + kThreads - 1) / kThreads), dim3(kThreads),
                      0, stream, a);
   HIP_CALL(hipGetLastError());
-  HIP_CALL(rocprim::inclusive_scan(scan_ws, scan_len, static_cast<const int64_t*>(a.deg),
-                                   a.cand_ptr + 1, size_t(a.f), rocprim::plus<int64_t>(),
-                                   stream));
-  scan_len = size_t(L.scan_len);
-  HIP_CALL(rocprim::inclusive_scan(scan_ws, scan_len, static_cast<const int64_t*>(a.nit),
-                                   a.item_ptr + 1, size_t(a.f), rocprim::plus<int64_t>(),
-                                   stream));
+  scan_i64(scan_ws, L.scan_len, a.deg, a.cand_ptr + 1, a.f, stream);
+  scan_i64(scan_ws, L.scan_len, a.nit, a.item_ptr + 1, a.f, stream);
   const dim3 per_item = grid_1d((a.bound + kWaves - 1) / kWaves);
-  hipLaunchKernelGGL(trv_item_rows_kernel, grid_1d((a.bound + kThreads - 1) / kThreads),
-                     dim3(kThreads), 0, stream, a);
+  launch_item_rows(a.f, a.bound, a.item_ptr, a.item_row, stream);
   hipLaunchKernelGGL((trv_claim_kernel<MODE>), per_item, dim3(kThreads), 0, stream, a);
   hipLaunchKernelGGL((trv_walk_kernel<MODE, false>), per_item, dim3(kThreads), 0, stream, a);
   HIP_CALL(hipGetLastError());
-  scan_len = size_t(L.scan_len);
-  HIP_CALL(rocprim::inclusive_scan(scan_ws, scan_len, static_cast<const int64_t*>(a.item_cnt),
-                                   a.item_base + 1, size_t(a.bound), rocprim::plus<int64_t>(),
-                                   stream));
+  scan_i64(scan_ws, L.scan_len, a.item_cnt, a.item_base + 1, a.bound, stream);
   hipLaunchKernelGGL((trv_walk_kernel<MODE, true>), per_item, dim3(kThreads), 0, stream, a);
   hipLaunchKernelGGL(trv_status_kernel, dim3(1), dim3(1), 0, stream, a);
   HIP_CALL(hipGetLastError());
@@ -461,7 +389,7 @@ int dglhip_bfs_init_device(int64_t num_nodes, int64_t nnz, const int64_t* indptr
   API_BEGIN();
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   check_graph(num_nodes, nnz);
-  check_not_capturing(stream);
+  check_not_capturing(stream, kNoCapture);
   DGLHIP_CHECK(num_sources >= 0 && num_sources < (int64_t(1) << 31),
                "bad number of sources " << num_sources);
   DGLHIP_CHECK(indptr && status && (num_sources == 0 || source) &&
@@ -488,15 +416,14 @@ int dglhip_topological_init_device(int64_t num_nodes, int64_t nnz, const int64_t
   API_BEGIN();
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   check_graph(num_nodes, nnz);
-  check_not_capturing(stream);
+  check_not_capturing(stream, kNoCapture);
   DGLHIP_CHECK(status, "null pointer argument");
   HIP_CALL(hipMemsetAsync(status, 0, 4 * sizeof(int64_t), stream));
   if (num_nodes == 0) return 0;
   DGLHIP_CHECK(indptr && opposite_indptr && claim && remain && out && workspace,
                "null pointer argument");
   const TopoLayout L(num_nodes);
-  DGLHIP_CHECK(workspace_bytes >= L.total, "workspace of " << workspace_bytes << " B, "
-                                                           << L.total << " needed");
+  check_workspace(workspace_bytes, L.total);
   char* ws = static_cast<char*>(workspace);
   TopoArgs t;
   t.N = num_nodes; t.nnz = nnz; t.waves = L.waves;
@@ -509,10 +436,7 @@ int dglhip_topological_init_device(int64_t num_nodes, int64_t nnz, const int64_t
   const dim3 grid = grid_1d((num_nodes + kThreads - 1) / kThreads);
   hipLaunchKernelGGL(topo_flag_kernel, grid, dim3(kThreads), 0, stream, t);
   HIP_CALL(hipGetLastError());
-  size_t scan_len = size_t(L.scan_len);
-  HIP_CALL(rocprim::inclusive_scan(ws + L.scan, scan_len, static_cast<const int64_t*>(t.wave_cnt),
-                                   t.wave_base + 1, size_t(L.waves), rocprim::plus<int64_t>(),
-                                   stream));
+  scan_i64(ws + L.scan, L.scan_len, t.wave_cnt, t.wave_base + 1, L.waves, stream);
   hipLaunchKernelGGL(topo_place_kernel, grid, dim3(kThreads), 0, stream, t);
   hipLaunchKernelGGL(topo_status_kernel, dim3(1), dim3(1), 0, stream, t);
   HIP_CALL(hipGetLastError());
@@ -529,7 +453,7 @@ int dglhip_traversal_level_device(int mode, int64_t num_nodes, int64_t nnz, cons
   API_BEGIN();
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   check_graph(num_nodes, nnz);
-  check_not_capturing(stream);
+  check_not_capturing(stream, kNoCapture);
   DGLHIP_CHECK(mode == kBfs || mode == kTopo, "unknown traversal mode " << mode);
   DGLHIP_CHECK(num_nodes >= 1 && frontier_len >= 1 && frontier_len < (int64_t(1) << 31) &&
                    num_candidates >= 0 && key_base >= 0 && next_capacity >= 0,
@@ -540,8 +464,7 @@ int dglhip_traversal_level_device(int mode, int64_t num_nodes, int64_t nnz, cons
                    (!next_edge || eid),
                "null pointer argument");
   const Layout L(frontier_len, num_candidates);
-  DGLHIP_CHECK(workspace_bytes >= L.total, "workspace of " << workspace_bytes << " B, "
-                                                           << L.total << " needed");
+  check_workspace(workspace_bytes, L.total);
   char* ws = static_cast<char*>(workspace);
   Args a;
   a.N = num_nodes; a.nnz = nnz; a.f = frontier_len; a.bound = L.bound;

@@ -29,15 +29,11 @@
 // Deterministic, no atomics; the host entry points run the same chains.
 #include <hip/hip_runtime.h>
 
-#include <rocprim/device/device_scan.hpp>
-
 #include <cstdlib>
 #include <type_traits>
 
 #include "../../include/dgl_hip.h"
-#include "common.h"
-#include "launch.h"
-#include "timing.h"
+#include "compact.h"
 
 namespace dglhip {
 
@@ -783,7 +779,7 @@ __global__ __launch_bounds__(256) void distmult_loss_final_kernel(
 }
 
 // The chunked item list (kernel._typed_items): items per row, scanned by
-// rocPRIM, then every item index's row by a binary search of item_ptr.
+// rocPRIM, then every item index's row by the shared search (compact.h).
 __global__ __launch_bounds__(256) void typed_nitems_kernel(int64_t num_rows,
                                                            const int64_t* __restrict__ ptr,
                                                            int64_t* __restrict__ nit) {
@@ -792,29 +788,6 @@ __global__ __launch_bounds__(256) void typed_nitems_kernel(int64_t num_rows,
   const int64_t deg = ptr[r + 1] - ptr[r];
   const int64_t c = (deg + kChunk - 1) / kChunk;
   nit[r] = c > 1 ? c : 1;
-}
-
-__global__ __launch_bounds__(256) void typed_item_rows_kernel(
-    int64_t num_rows, int64_t bound, const int64_t* __restrict__ item_ptr,
-    int32_t* __restrict__ item_row) {
-  const int64_t j = block_linear() * blockDim.x + threadIdx.x;
-  if (j >= bound) return;
-  // the row r with item_ptr[r] <= j < item_ptr[r + 1]; num_rows past the last
-  int64_t lo = 0, hi = num_rows;  // answer in [lo, hi]
-  while (lo < hi) {
-    const int64_t mid = (lo + hi + 1) >> 1;
-    if (item_ptr[mid] <= j) lo = mid;
-    else hi = mid - 1;
-  }
-  item_row[j] = static_cast<int32_t>(lo);
-}
-
-size_t typed_items_scan_bytes(int64_t num_rows) {
-  size_t bytes = 0;
-  HIP_CALL(rocprim::inclusive_scan(nullptr, bytes, static_cast<const int64_t*>(nullptr),
-                                   static_cast<int64_t*>(nullptr), size_t(num_rows),
-                                   rocprim::plus<int64_t>()));
-  return bytes;
 }
 
 }  // namespace
@@ -1084,7 +1057,7 @@ int dglhip_typed_block_wgrad_device(int64_t num_rels, int64_t num_items, int64_t
 int64_t dglhip_typed_items_workspace_bytes(int64_t num_rows) {
   try {
     if (num_rows <= 0) return 0;
-    return ((num_rows * 8 + 255) & ~int64_t(255)) + int64_t(typed_items_scan_bytes(num_rows));
+    return round256(num_rows * 8) + int64_t(scan_bytes_i64(num_rows));
   } catch (const std::exception& e) {
     set_last_error(e.what());
     return -1;
@@ -1100,27 +1073,19 @@ int dglhip_typed_items_device(int64_t num_rows, const int64_t* ptr, int64_t boun
   DGLHIP_CHECK(item_ptr, "null pointer argument");
   HIP_CALL(hipMemsetAsync(item_ptr, 0, sizeof(int64_t), stream));
   if (num_rows == 0) {
-    if (bound > 0) {
-      hipLaunchKernelGGL(typed_item_rows_kernel, grid_1d((bound + 255) / 256), dim3(256), 0,
-                         stream, num_rows, bound, item_ptr, item_row);
-    }
+    if (bound > 0) launch_item_rows(num_rows, bound, item_ptr, item_row, stream);
     return 0;
   }
   DGLHIP_CHECK(ptr && item_row && workspace, "null pointer argument");
-  const int64_t need = dglhip_typed_items_workspace_bytes(num_rows);
-  DGLHIP_CHECK(workspace_bytes >= need, "workspace of " << workspace_bytes << " B, "
-                                                        << need << " needed");
+  check_workspace(workspace_bytes, dglhip_typed_items_workspace_bytes(num_rows));
   char* ws = static_cast<char*>(workspace);
   int64_t* nit = reinterpret_cast<int64_t*>(ws);
-  const int64_t nb = (num_rows * 8 + 255) & ~int64_t(255);
-  size_t tmp = size_t(workspace_bytes - nb);
+  const int64_t nb = round256(num_rows * 8);
   hipLaunchKernelGGL(typed_nitems_kernel, grid_1d((num_rows + 255) / 256), dim3(256), 0, stream,
                      num_rows, ptr, nit);
   HIP_CALL(hipGetLastError());
-  HIP_CALL(rocprim::inclusive_scan(ws + nb, tmp, static_cast<const int64_t*>(nit), item_ptr + 1,
-                                   size_t(num_rows), rocprim::plus<int64_t>(), stream));
-  hipLaunchKernelGGL(typed_item_rows_kernel, grid_1d((bound + 255) / 256), dim3(256), 0, stream,
-                     num_rows, bound, item_ptr, item_row);
+  scan_i64(ws + nb, workspace_bytes - nb, nit, item_ptr + 1, num_rows, stream);
+  launch_item_rows(num_rows, bound, item_ptr, item_row, stream);
   HIP_CALL(hipGetLastError());
   API_END();
 }

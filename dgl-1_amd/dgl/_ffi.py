@@ -14,7 +14,7 @@ from __future__ import absolute_import
 import ctypes
 import os
 
-import torch  # noqa: F401  (loads the HIP runtime torch links against first)
+import torch  # (also loads the HIP runtime torch links against first)
 
 from .base import DGLError
 
@@ -345,6 +345,11 @@ def ptr(t):
     if t is None:
         return None
     return ctypes.c_void_p(t.data_ptr())
+
+
+def stream_of(device):
+    """The current stream of a ROCm ``device`` as the library's ``void*``."""
+    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
 # --------------------------------------------------------------------------

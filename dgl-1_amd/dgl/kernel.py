@@ -34,8 +34,14 @@ import numpy as np
 import torch
 
 from . import _ffi, _handoff
-from ._ffi import LIB, check_call, ptr
+from ._ffi import LIB, check_call, ptr, stream_of as _stream_of
 from .base import DGLError
+# graph_index, the tools and the tests reach the device graph builders as kernel.<name>
+from .device_graph import (  # noqa: F401
+    SUBGRAPH_CHUNK, LINE_GRAPH_TILE, TRAVERSAL_CHUNK, SAMPLE_REG_SLOTS, _workspace,
+    induced_subgraph_count, induced_subgraph_fill, induced_subgraph,
+    line_graph_count, line_graph_fill, line_graph,
+    bfs_frontiers, topological_frontiers, sample_mix, neighbor_sample)
 
 __all__ = ["CSR", "SparseAdj", "build_csr", "gspmm", "gsddmm_dot",
            "MSG_COPY_U", "MSG_U_MUL_E", "MSG_COPY_E", "RED_SUM", "RED_MAX", "RED_MEAN"]
@@ -229,11 +235,6 @@ def _split_threshold(csr, waves=None):
     check_call(LIB.dglhip_spmm_split_threshold(int(csr.nnz), int(csr.max_degree), int(R),
                                                ctypes.byref(t)))
     return int(t.value)
-
-
-
-def _stream_of(device):
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
 class CSR(object):
@@ -1767,9 +1768,7 @@ def _typed_items(rowptr, nnz):
         item_ptr = torch.empty(R + 1, dtype=torch.int64, device=rowptr.device)
         item_row = torch.empty(max(bound, 1), dtype=torch.int32, device=rowptr.device)[:bound]
         nb = LIB.dglhip_typed_items_workspace_bytes(R)
-        if nb < 0:
-            check_call(-1)
-        ws = torch.empty(max(int(nb), 1), dtype=torch.uint8, device=rowptr.device)
+        ws = _workspace(nb, rowptr.device)
         check_call(LIB.dglhip_typed_items_device(R, ptr(rowptr), bound,
                                                  ptr(item_ptr), ptr(item_row), ptr(ws), int(nb),
                                                  _stream_of(rowptr.device)))
@@ -2725,394 +2724,3 @@ def segment_reduce(x, offsets, reduce, weight=None):
     if x.dim() == 2:
         return _SegmentReduce.apply(x, w, segs, red)
     return _SegmentReduce.apply(x.reshape(N, F), w, segs, red).view((B,) + fshape)
-
-
-# ---------------------------------------------------------------------------
-# Node-induced subgraph on the device (csrc/induced_subgraph.hip)
-# ---------------------------------------------------------------------------
-SUBGRAPH_CHUNK = 512  # DGLHIP_SUBGRAPH_CHUNK: slots per item of the subgraph walk
-
-
-def induced_subgraph_count(csr, sel):
-    """Stage A of :func:`induced_subgraph` over the source-major ``csr`` and
-    the int64 device ids ``sel``: (workspace, [edges, invalid ids, duplicate
-    positions, items]), the four counts read once through pinned memory."""
-    dev = csr.device
-    N, n, nnz = csr.num_rows, sel.numel(), csr.nnz
-    nbytes = LIB.dglhip_induced_subgraph_workspace_bytes(N, n, nnz)
-    if nbytes < 0:
-        check_call(-1)
-    ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
-    status = torch.empty(4, dtype=torch.int64, device=dev)
-    check_call(LIB.dglhip_induced_subgraph_count_device(
-        N, n, nnz, ptr(csr.indptr), ptr(csr.indices) if nnz else None, ptr(sel) if n else None,
-        ptr(ws), int(nbytes), ptr(status), _stream_of(dev)))
-    host = torch.empty(4, dtype=torch.int64, pin_memory=True)
-    host.copy_(status, non_blocking=True)
-    torch.cuda.current_stream(dev).synchronize()
-    return ws, host.tolist()
-
-
-def induced_subgraph_fill(csr, sel, ws, items, m):
-    """Stage B: (src', dst', parent_eid), int64[m] each, on the device."""
-    dev = csr.device
-    out = torch.empty(3, m, dtype=torch.int64, device=dev)
-    if m:
-        check_call(LIB.dglhip_induced_subgraph_fill_device(
-            csr.num_rows, sel.numel(), csr.nnz, ptr(csr.indptr), ptr(csr.indices), ptr(csr.eid),
-            ptr(sel), ptr(ws), ws.numel(), int(items), int(m), ptr(out[0]), ptr(out[1]),
-            ptr(out[2]), _stream_of(dev)))
-    return out[0], out[1], out[2]
-
-
-def induced_subgraph(csr, sel):
-    """The subgraph of a graph induced by the nodes ``sel`` (int64, on the
-    device of ``csr``), from the graph's source-major CSR in edge-id order
-    (``SparseAdj.bwd`` of an ORDER_EID adjacency): ``(src', dst', parent_eid)``
-    with subgraph node ``i`` = ``sel[i]`` and the edges in the order of the
-    native index's vertex_subgraph (the out-edges of ``sel[0]``, ``sel[1]``,
-    ... in edge-id order that end inside the set).
-
-    One host read per call (the edge count and the validation counters), so
-    it cannot run while the current stream is being captured. An id outside
-    the graph or listed twice raises DGLError."""
-    dev = csr.device
-    if dev.type != "cuda":
-        raise DGLError("the device route of subgraph() needs a CSR on a ROCm device")
-    if torch.cuda.is_current_stream_capturing():
-        raise DGLError("subgraph() of device ids reads the subgraph's size on the host: "
-                       "it cannot run while a stream is being captured")
-    if sel.dtype.is_floating_point or sel.dtype == torch.bool:
-        raise DGLError("Index data must be an integer tensor, got %s" % sel.dtype)
-    sel = sel.detach().to(device=dev, dtype=torch.int64).reshape(-1).contiguous()
-    ws, (m, invalid, dup, items) = induced_subgraph_count(csr, sel)
-    if invalid:
-        raise DGLError("Invalid vertex: %d of the %d ids are not in a graph of %d nodes"
-                       % (invalid, sel.numel(), csr.num_rows))
-    if dup:
-        raise DGLError("subgraph() of device ids needs distinct nodes: %d of the %d ids repeat "
-                       "an earlier one" % (dup, sel.numel()))
-    return induced_subgraph_fill(csr, sel, ws, items, m)
-
-
-# ---------------------------------------------------------------------------
-# Line graph on the device (csrc/line_graph.hip)
-# ---------------------------------------------------------------------------
-LINE_GRAPH_TILE = 256  # DGLHIP_LINE_GRAPH_TILE: candidates per work unit
-
-
-def line_graph_count(csr_bwd, src, dst, backtracking):
-    """Stage A of :func:`line_graph`: (workspace, [line-graph edges M,
-    candidates K, invalid endpoints, work units]), the four counts read once
-    through pinned memory."""
-    dev = csr_bwd.device
-    N, E = csr_bwd.num_rows, src.numel()
-    nbytes = LIB.dglhip_line_graph_workspace_bytes(N, E)
-    if nbytes < 0:
-        check_call(-1)
-    ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
-    status = torch.empty(4, dtype=torch.int64, device=dev)
-    check_call(LIB.dglhip_line_graph_count_device(
-        N, E, ptr(src) if E else None, ptr(dst) if E else None, ptr(csr_bwd.indptr),
-        ptr(csr_bwd.indices) if E else None, int(bool(backtracking)), ptr(ws), int(nbytes),
-        ptr(status), _stream_of(dev)))
-    host = torch.empty(4, dtype=torch.int64, pin_memory=True)
-    host.copy_(status, non_blocking=True)
-    torch.cuda.current_stream(dev).synchronize()
-    return ws, host.tolist()
-
-
-def line_graph_fill(csr_bwd, src, dst, backtracking, ws, units, m):
-    """Stage B: (lsrc, ldst), int64[m] each, on the device."""
-    dev = csr_bwd.device
-    out = torch.empty(2, m, dtype=torch.int64, device=dev)
-    if m:
-        check_call(LIB.dglhip_line_graph_fill_device(
-            csr_bwd.num_rows, src.numel(), ptr(src), ptr(dst), ptr(csr_bwd.indptr),
-            ptr(csr_bwd.indices), ptr(csr_bwd.eid), int(bool(backtracking)), ptr(ws),
-            ws.numel(), int(units), int(m), ptr(out[0]), ptr(out[1]), _stream_of(dev)))
-    return out[0], out[1]
-
-
-def line_graph(csr_bwd, src, dst, backtracking):
-    """The edge list of the line graph of a graph, from its endpoints ``src``,
-    ``dst`` in edge-id order (int64, on the device of ``csr_bwd``) and its
-    source-major CSR in edge-id order (``SparseAdj.bwd`` of an ORDER_EID
-    adjacency): ``(lsrc, ldst)`` in the order of the native index's
-    line_graph (for edge i = (u, v), the out-edges of v in edge-id order,
-    without those back to u unless ``backtracking``).
-
-    One host read per call (the edge count and the validation counter), so it
-    cannot run while the current stream is being captured. An endpoint
-    outside the graph raises DGLError, and so does a line graph whose edge
-    list would not fit in the device's free memory: its size is quadratic in
-    the degree of a hub."""
-    dev = csr_bwd.device
-    if dev.type != "cuda":
-        raise DGLError("the device route of line_graph() needs a CSR on a ROCm device")
-    if torch.cuda.is_current_stream_capturing():
-        raise DGLError("line_graph() on a device reads the line graph's size on the host: "
-                       "it cannot run while a stream is being captured")
-    src = src.detach().to(device=dev, dtype=torch.int64).reshape(-1).contiguous()
-    dst = dst.detach().to(device=dev, dtype=torch.int64).reshape(-1).contiguous()
-    if src.numel() != dst.numel() or src.numel() != csr_bwd.nnz:
-        raise DGLError("line_graph(): %d sources, %d destinations and a CSR of %d edges"
-                       % (src.numel(), dst.numel(), csr_bwd.nnz))
-    ws, (m, _, invalid, units) = line_graph_count(csr_bwd, src, dst, backtracking)
-    if invalid:
-        raise DGLError("Invalid vertex: %d endpoints of the %d edges are not in a graph of %d "
-                       "nodes" % (invalid, src.numel(), csr_bwd.num_rows))
-    need = 16 * m
-    free = torch.cuda.mem_get_info(dev)[0]
-    if need > free:
-        raise DGLError("the line graph has M = %d edges: its edge list needs %d bytes and the "
-                       "device has %d free" % (m, need, free))
-    return line_graph_fill(csr_bwd, src, dst, backtracking, ws, units, m)
-
-
-# ---------------------------------------------------------------------------
-# BFS and topological frontiers on the device (csrc/traversal.hip)
-# ---------------------------------------------------------------------------
-TRAVERSAL_CHUNK = 512  # DGLHIP_TRAVERSAL_CHUNK: slots per item of a level's walk
-_TRAVERSE_BFS, _TRAVERSE_TOPOLOGICAL = 0, 1
-
-
-class _LevelLoop(object):
-    """The host side of a device traversal: the status read after every call
-    (one pinned buffer for the whole traversal), the level workspace (grown,
-    never shrunk) and the queue bookkeeping."""
-
-    def __init__(self, csr, mode, queue, num_done, edges=None):
-        self.csr, self.mode, self.dev = csr, mode, csr.device
-        self.queue, self.edges = queue, edges
-        self.edge_shift = num_done  # BFS edges: queue position of edge 0's node
-        self.status = torch.empty(4, dtype=torch.int64, device=self.dev)
-        self.host = torch.empty(4, dtype=torch.int64, pin_memory=True)
-        self.ws = None
-        self.sections = []
-
-    def read_status(self):
-        self.host.copy_(self.status, non_blocking=True)
-        torch.cuda.current_stream(self.dev).synchronize()
-        return self.host.tolist()
-
-    def run(self, size, cand, claim, visited, remain):
-        """Levels until a frontier is empty, from the frontier queue[0:size]
-        whose rows hold ``cand`` slots; returns the queue length."""
-        csr, nnz = self.csr, self.csr.nnz
-        off, key_base = 0, 1
-        eid = csr.eid if self.edges is not None else None
-        while size > 0:
-            self.sections.append(size)
-            nxt = off + size
-            nbytes = LIB.dglhip_traversal_level_workspace_bytes(size, cand)
-            if nbytes < 0:
-                check_call(-1)
-            if self.ws is None or self.ws.numel() < nbytes:
-                self.ws = torch.empty(int(nbytes), dtype=torch.uint8, device=self.dev)
-            cap = self.queue.numel() - nxt
-            check_call(LIB.dglhip_traversal_level_device(
-                self.mode, csr.num_rows, nnz, ptr(csr.indptr), ptr(csr.indices) if nnz else None,
-                ptr(eid), ptr(self.queue[off:]), size, cand,
-                key_base if self.mode == _TRAVERSE_TOPOLOGICAL else 0, ptr(claim), ptr(visited),
-                ptr(remain), ptr(self.queue[nxt:]) if cap else None,
-                ptr(self.edges[nxt - self.edge_shift:])
-                if self.edges is not None and cap else None,
-                cap, ptr(self.ws), self.ws.numel(), ptr(self.status), _stream_of(self.dev)))
-            new_size, new_cand, invalid, items = self.read_status()
-            if invalid or new_size > cap or items > size + cand // TRAVERSAL_CHUNK + 1:
-                raise DGLError("device traversal: inconsistent level (%d invalid ids, %d of %d "
-                               "queue slots, %d items)" % (invalid, new_size, cap, items))
-            key_base += cand
-            off, size, cand = nxt, new_size, new_cand
-        return off
-
-
-def _check_traversal(csr):
-    if csr.device.type != "cuda":
-        raise DGLError("the device route of a traversal needs a CSR on a ROCm device")
-    if torch.cuda.is_current_stream_capturing():  # before anything is launched
-        raise DGLError("a traversal reads every frontier's size on the host: it cannot run "
-                       "while a stream is being captured")
-
-
-def bfs_frontiers(csr, source, edges=False):
-    """Breadth-first frontiers over ``csr`` (rows = the node walked from, in
-    the native index's slot order: ``SparseAdj.bwd`` of an ORDER_EID adjacency
-    forward, ``.fwd`` in reverse) from the int64 device ids ``source``:
-    ``(ids, sections)`` with ``ids`` on the device, as the host route's
-    ``_CAPI_DGLBFSNodes`` (``_CAPI_DGLBFSEdges`` with ``edges``) gives them,
-    element for element. One host read per level; an id outside the graph
-    raises DGLError."""
-    _check_traversal(csr)
-    dev, N = csr.device, csr.num_rows
-    if source.dtype.is_floating_point or source.dtype == torch.bool:
-        raise DGLError("Index data must be an integer tensor, got %s" % source.dtype)
-    source = source.detach().to(device=dev, dtype=torch.int64).reshape(-1).contiguous()
-    n = source.numel()
-    if n == 0:
-        return torch.empty(0, dtype=torch.int64, device=dev), []
-    queue = torch.empty(n + N, dtype=torch.int64, device=dev)
-    queue[:n] = source
-    claim = torch.empty(N, dtype=torch.int64, device=dev)
-    visited = torch.empty(N, dtype=torch.uint8, device=dev)
-    loop = _LevelLoop(csr, _TRAVERSE_BFS, queue, n,
-                      torch.empty(N, dtype=torch.int64, device=dev) if edges else None)
-    check_call(LIB.dglhip_bfs_init_device(N, csr.nnz, ptr(csr.indptr), ptr(source), n,
-                                          ptr(claim) if N else None, ptr(visited) if N else None,
-                                          ptr(loop.status), _stream_of(dev)))
-    _, cand, invalid, _ = loop.read_status()
-    if invalid:
-        raise DGLError("Invalid source vertex: %d of the %d ids are not in a graph of %d nodes"
-                       % (invalid, n, N))
-    end = loop.run(n, cand, claim, visited, None)
-    if edges:
-        return loop.edges[:end - n], loop.sections[1:]
-    return queue[:end], loop.sections
-
-
-def topological_frontiers(csr, opposite):
-    """Topological (Kahn) frontiers over ``csr``, with ``opposite`` the CSR of
-    the other direction (its row lengths are the counters): ``(ids,
-    sections)`` as ``_CAPI_DGLTopologicalNodes`` gives them, ``ids`` on the
-    device. Raises DGLError when the graph has a loop."""
-    _check_traversal(csr)
-    dev, N = csr.device, csr.num_rows
-    if N == 0:
-        return torch.empty(0, dtype=torch.int64, device=dev), []
-    queue = torch.empty(N, dtype=torch.int64, device=dev)
-    claim = torch.empty(N, dtype=torch.int64, device=dev)
-    remain = torch.empty(N, dtype=torch.int64, device=dev)
-    loop = _LevelLoop(csr, _TRAVERSE_TOPOLOGICAL, queue, 0)
-    nbytes = LIB.dglhip_topological_init_workspace_bytes(N)
-    if nbytes < 0:
-        check_call(-1)
-    loop.ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
-    check_call(LIB.dglhip_topological_init_device(
-        N, csr.nnz, ptr(csr.indptr), ptr(opposite.indptr), ptr(claim), ptr(remain), ptr(queue),
-        ptr(loop.ws), loop.ws.numel(), ptr(loop.status), _stream_of(dev)))
-    size, cand, _, _ = loop.read_status()
-    end = loop.run(size, cand, claim, None, remain)
-    if end != N:
-        raise DGLError("Error in topological traversal: loop detected in the given graph.")
-    return queue, loop.sections
-
-
-# ---------------------------------------------------------------------------
-# Uniform neighbour sampling (csrc/neighbor_sample.hip, neighbor_sample_host.cc)
-# ---------------------------------------------------------------------------
-SAMPLE_REG_SLOTS = 256  # DGLHIP_SAMPLE_REG_SLOTS: the longest row selected from registers
-_U64 = (1 << 64) - 1
-
-
-def sample_mix(z):
-    """The hash of the sampling rule (csrc/sample_key.h) of the integer ``z``
-    taken modulo 2^64."""
-    return int(LIB.dglhip_sample_mix(int(z) & _U64))
-
-
-def _neighbor_sample_host(csr, seeds, num_hops, k, seed, in_dir):
-    seeds = seeds.cpu()
-    N, nnz = csr.num_rows, csr.nnz
-    sizes = torch.zeros(2, dtype=torch.int64)
-    check_call(LIB.dglhip_neighbor_sample_host(
-        N, nnz, ptr(csr.indptr), ptr(csr.indices) if nnz else None,
-        ptr(csr.eid) if nnz else None, int(in_dir), ptr(seeds) if seeds.numel() else None,
-        seeds.numel(), num_hops, k, seed, ptr(sizes)))
-    nv, m = sizes.tolist()
-    nodes = torch.empty(2, nv, dtype=torch.int64)
-    edges = torch.empty(3, m, dtype=torch.int64)
-    check_call(LIB.dglhip_neighbor_sample_host_fetch(
-        nv, m, ptr(nodes[0]), ptr(nodes[1]), ptr(edges[0]), ptr(edges[1]), ptr(edges[2])))
-    return nodes[0], nodes[1], edges[0], edges[1], edges[2]
-
-
-def neighbor_sample(csr, seeds, num_hops, k, seed, in_dir=True, timings=None):
-    """The ``num_hops``-hop neighbourhood of the int64 ids ``seeds`` sampled
-    at fan-out ``k`` over ``csr`` (rows = the vertex expanded:
-    ``SparseAdj.fwd`` with ``in_dir``, ``.bwd`` without) by the stateless rule
-    of csrc/sample_key.h under the 64-bit ``seed``: ``(vertices, layers,
-    sub_src, sub_dst, parent_eid)``, int64 on the device of ``csr``.
-
-    ``vertices`` are the visited parent ids ascending and ``layers`` the hop
-    that reached each (seeds: 0); the edges are the selected slots of every
-    vertex of layer < num_hops in ascending id, each row in ascending
-    position, as endpoints in ``vertices`` plus the parent edge id. The arrays
-    depend on the arguments alone: the HIP route (a CSR on a ROCm device) and
-    the host twin (a CSR in host memory) give the same ones, bit for bit.
-
-    On a device there is one host read for the seeds and one per hop, so it
-    cannot run while the current stream is being captured. A seed outside the
-    graph raises DGLError. ``timings`` (a dict) receives device events around
-    the hop loop and the final stage."""
-    num_hops, k, seed = int(num_hops), int(k), int(seed) & _U64
-    if num_hops < 0 or k < 0:
-        raise DGLError("invalid sampling parameters: %d hops, fan-out %d" % (num_hops, k))
-    if seeds.dtype.is_floating_point or seeds.dtype == torch.bool:
-        raise DGLError("Index data must be an integer tensor, got %s" % seeds.dtype)
-    dev = csr.device
-    seeds = seeds.detach().to(dtype=torch.int64).reshape(-1).contiguous()
-    if dev.type != "cuda":
-        return _neighbor_sample_host(csr, seeds, num_hops, k, seed, in_dir)
-    if torch.cuda.is_current_stream_capturing():  # before anything is launched
-        raise DGLError("neighbour sampling reads every frontier's size on the host: it cannot "
-                       "run while a stream is being captured")
-    seeds = seeds.to(dev)
-    N, nnz, n = csr.num_rows, csr.nnz, seeds.numel()
-    stream = _stream_of(dev)
-    status = torch.empty(4, dtype=torch.int64, device=dev)
-    host = torch.empty(4, dtype=torch.int64, pin_memory=True)
-
-    def read_status():
-        host.copy_(status, non_blocking=True)
-        torch.cuda.current_stream(dev).synchronize()
-        return host.tolist()
-
-    if timings is not None:
-        marks = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
-        marks[0].record()
-    layer = torch.empty(N, dtype=torch.int32, device=dev)
-    front = torch.empty(n, dtype=torch.int64, device=dev)
-    check_call(LIB.dglhip_neighbor_sample_init_device(
-        N, ptr(seeds) if n else None, n, ptr(layer) if N else None, ptr(front) if n else None,
-        ptr(status), stream))
-    size, invalid, _, _ = read_status()
-    if invalid:
-        raise DGLError("Invalid vertex: %d of the %d seeds are not in a graph of %d nodes"
-                       % (invalid, n, N))
-    nv, m = size, 0
-    for hop in range(num_hops):
-        if size == 0 or k == 0:
-            break
-        cap = min(N - nv, size * k)
-        nxt = torch.empty(cap, dtype=torch.int64, device=dev)
-        check_call(LIB.dglhip_neighbor_sample_hop_device(
-            N, nnz, ptr(csr.indptr), ptr(csr.indices) if nnz else None, ptr(front), size, hop, k,
-            seed, ptr(layer), ptr(nxt) if cap else None, cap, ptr(status), stream))
-        new_size, _, edges, _ = read_status()
-        if new_size > cap or edges > nnz - m:
-            raise DGLError("device sampling: inconsistent hop (%d of %d frontier slots, %d "
-                           "edges)" % (new_size, cap, edges))
-        front, size = nxt, new_size
-        nv += new_size
-        m += edges
-    if timings is not None:
-        marks[1].record()
-    nodes = torch.empty(2, nv, dtype=torch.int64, device=dev)
-    out = torch.empty(3, m, dtype=torch.int64, device=dev)
-    if nv:
-        nbytes = LIB.dglhip_neighbor_sample_workspace_bytes(N, nv)
-        if nbytes < 0:
-            check_call(-1)
-        ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
-        check_call(LIB.dglhip_neighbor_sample_final_device(
-            N, nnz, ptr(csr.indptr), ptr(csr.indices) if nnz else None,
-            ptr(csr.eid) if m else None, int(bool(in_dir)), num_hops, k, seed, ptr(layer), nv, m,
-            ptr(nodes[0]), ptr(nodes[1]), ptr(out[0]) if m else None, ptr(out[1]) if m else None,
-            ptr(out[2]) if m else None, ptr(ws), int(nbytes), stream))
-    if timings is not None:
-        marks[2].record()
-        marks[2].synchronize()
-        timings["hops_ms"] = marks[0].elapsed_time(marks[1])
-        timings["final_ms"] = marks[1].elapsed_time(marks[2])
-    return nodes[0], nodes[1], out[0], out[1], out[2]

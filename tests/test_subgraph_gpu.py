@@ -281,3 +281,30 @@ def test_c_abi_entry_points(case):
         ptr(out), stream) == -1
     assert b"workspace" in LIB.DGLGetLastError()
     assert kernel.SUBGRAPH_CHUNK == SUBGRAPH_CHUNK
+
+
+def test_rows_at_exact_multiples_of_the_chunk():
+    """Rows of out-degree 0, 1, K - 1, K, K + 1 and 2K: a row of exactly
+    deg / K whole items and no partial one, followed by rows without items.
+    Isolated nodes lie between the rows and at both ends of the id range, so
+    the item search skips empty positions everywhere."""
+    K = SUBGRAPH_CHUNK
+    degs = [0, 1, K - 1, K, K + 1, 2 * K]
+    rows = 1 + 2 * np.arange(len(degs))  # odd ids; the even ids between them are isolated
+    first = 2 * len(degs) + 1            # the targets are first .. first + 2K - 1
+    n = first + 2 * K + 1                # node 0 and node n - 1 are isolated
+    src = np.concatenate([np.full(d, r) for r, d in zip(rows, degs)])
+    dst = np.concatenate([first + np.arange(d) for d in degs])
+    assert n == 2 * K + 14 and src.size == 5 * K + 1
+    g = dgl.DGLGraph(multigraph=True)
+    g.add_nodes(n)
+    g.add_edges(src, dst)
+    # without the row of K + 1 slots and every third target
+    fewer = np.setdiff1d(np.arange(n), np.concatenate([rows[4:5], first + np.arange(0, 2 * K, 3)]))
+    for sel in (np.arange(n), fewer, fewer[::-1].copy()):
+        dev = g.subgraph(torch.from_numpy(sel).cuda())
+        same_subgraph(dev, g.subgraph(sel.tolist()))
+    assert dev.number_of_edges() > K
+    csr = g._graph.adjacency(torch.device("cuda", torch.cuda.current_device())).bwd
+    _, (m, invalid, dup, items) = kernel.induced_subgraph_count(csr, torch.arange(n).cuda())
+    assert (m, invalid, dup, items) == (src.size, 0, 0, 0 + 1 + 1 + 1 + 2 + 2)

@@ -361,3 +361,37 @@ def test_prop_nodes_bfs_on_device_features(case):
     dev = run("cuda", case.device_source("island"))
     assert dev.is_cuda and torch.equal(dev.cpu(), host)
     assert not torch.equal(host, torch.arange(N, dtype=torch.float32).reshape(N, 1) % 7)
+
+
+# ---------------------------------------------------------------- chunk edges
+def test_bfs_rows_at_exact_multiples_of_the_chunk():
+    """One level whose frontier rows have out-degree 0, 1, K - 1, K, K + 1 and
+    2K: a row of exactly deg / K whole items and no partial one, followed by
+    rows without items; the frontier starts and ends with a row without items.
+    Isolated nodes lie between the rows and at both ends of the id range."""
+    K = TRAVERSAL_CHUNK
+    degs = [0, 1, K - 1, K, K + 1, 2 * K]
+    rows = (1 + 2 * np.arange(len(degs))).tolist()  # odd ids; the even ids between: isolated
+    first = 2 * len(degs) + 1                       # the targets are first .. first + 2K - 1
+    ends = [first + 2 * K + i for i in range(3)]    # reached, without out-edges
+    source = ends[-1] + 1
+    n = source + 2                                  # node 0 and node n - 1 are isolated
+    level1 = [ends[0]] + rows[:4] + [ends[1]] + rows[4:] + [ends[2]]
+    src = np.concatenate([np.full(len(level1), source)] +
+                         [np.full(d, r) for r, d in zip(rows, degs)])
+    dst = np.concatenate([level1] + [first + np.arange(d) for d in degs])
+    assert n == 2 * K + 18 and src.size == 5 * K + 10
+    src, dst = src.tolist(), dst.tolist()
+    g = dgl.DGLGraph(multigraph=True)
+    g.add_nodes(n)
+    g.add_edges(src, dst)
+    want_nodes, want_edges = check_bfs(slot_rows(n, src, dst), [source])
+    assert want_nodes[1] == level1 and len(want_nodes[2]) == 2 * K and len(want_nodes) == 3
+    dev_source = torch.tensor([source]).cuda()
+    dev_nodes = dgl.bfs_nodes_generator(g, dev_source)
+    dev_edges = dgl.bfs_edges_generator(g, dev_source)
+    on_device(dev_nodes)
+    on_device(dev_edges)
+    assert lists(dev_nodes) == want_nodes and lists(dev_edges) == want_edges
+    same_frontiers(dev_nodes, dgl.bfs_nodes_generator(g, [source]))
+    same_frontiers(dev_edges, dgl.bfs_edges_generator(g, [source]))
