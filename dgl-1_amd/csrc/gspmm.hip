@@ -22,6 +22,7 @@
 //    sequential chains start first and the tail is short.
 
 #include "gspmm_impl.h"
+#include "spmm_plan.h"
 
 namespace dglhip {
 
@@ -498,6 +499,29 @@ static void check_ufeat_ld(int64_t ufeat_ld, int64_t feat_len) {
                "ufeat_ld " << ufeat_ld << ": 0, feat_len, or an even width > feat_len");
 }
 
+void gspmm_items_columns(int msg_op, int64_t num_items, int64_t feat_len, const int32_t* item_rows,
+                         const int64_t* item_ptr, int accumulate, const int32_t* indices,
+                         const int64_t* eid, const float* ufeat, int64_t ufeat_ld,
+                         int64_t ufeat_rows, int items_per_wave, int column_parts,
+                         const float* efeat, int64_t efeat_len, float* out, int64_t out_rows,
+                         hipStream_t stream) {
+  DGLHIP_CHECK(msg_op >= 0 && msg_op <= 3, "unknown msg op " << msg_op);
+  DGLHIP_CHECK(num_items >= 0 && feat_len >= 0 && ufeat_rows >= 0 && out_rows >= 0,
+               "negative size");
+  DGLHIP_CHECK(items_per_wave == 1 || items_per_wave == 2,
+               "items_per_wave " << items_per_wave << ": 1 or 2");
+  DGLHIP_CHECK(column_parts == 1 || column_parts == 2,
+               "column_parts " << column_parts << ": 1 or 2");
+  if (num_items == 0 || feat_len == 0) return;
+  DGLHIP_CHECK(item_rows && item_ptr && indices && out, "null items/indices/out");
+  const int64_t elen = check_operands(msg_op, feat_len, ufeat, efeat, efeat_len);
+  check_ufeat_ld(ufeat_ld, feat_len);
+  SumLaunch a{num_items, feat_len, elen, nullptr, indices, eid, ufeat, efeat,
+              out, item_rows, item_ptr, item_ptr + 1, accumulate != 0, false, ufeat_ld,
+              ufeat_rows, items_per_wave, items_per_wave == 2 ? column_parts : 1, out_rows};
+  dispatch_sum(msg_op, false, a, stream);
+}
+
 }  // namespace dglhip
 
 using namespace dglhip;
@@ -610,21 +634,11 @@ int dglhip_gspmm_items_columns_device(int msg_op, int64_t num_items, int64_t fea
                                       int items_per_wave, int column_parts, const float* efeat,
                                       int64_t efeat_len, float* out, void* stream_) {
   API_BEGIN();
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  DGLHIP_CHECK(msg_op >= 0 && msg_op <= 3, "unknown msg op " << msg_op);
-  DGLHIP_CHECK(num_items >= 0 && feat_len >= 0 && ufeat_rows >= 0, "negative size");
-  DGLHIP_CHECK(items_per_wave == 1 || items_per_wave == 2,
-               "items_per_wave " << items_per_wave << ": 1 or 2");
-  DGLHIP_CHECK(column_parts == 1 || column_parts == 2,
-               "column_parts " << column_parts << ": 1 or 2");
-  if (num_items == 0 || feat_len == 0) return 0;
-  DGLHIP_CHECK(item_rows && item_ptr && indices && out, "null items/indices/out");
-  const int64_t elen = check_operands(msg_op, feat_len, ufeat, efeat, efeat_len);
-  check_ufeat_ld(ufeat_ld, feat_len);
-  SumLaunch a{num_items, feat_len, elen, nullptr, indices, eid, ufeat, efeat,
-              out, item_rows, item_ptr, item_ptr + 1, accumulate != 0, false, ufeat_ld,
-              ufeat_rows, items_per_wave, items_per_wave == 2 ? column_parts : 1};
-  dispatch_sum(msg_op, false, a, stream);
+  // the rows of out are not among the arguments: column_parts 2 runs the pair
+  // kernel here (the same bits); the plan calls gspmm_items_columns itself
+  gspmm_items_columns(msg_op, num_items, feat_len, item_rows, item_ptr, accumulate, indices, eid,
+                      ufeat, ufeat_ld, ufeat_rows, items_per_wave, column_parts, efeat, efeat_len,
+                      out, 0, static_cast<hipStream_t>(stream_));
   API_END();
 }
 

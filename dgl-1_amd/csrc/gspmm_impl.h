@@ -482,19 +482,25 @@ __device__ __forceinline__ uint32_t row_broadcast(uint32_t v, int j) {
 // reading item t's slot k + j and turning it into the row's byte offset (or,
 // past the item's end, an offset past the table, which the descriptor's
 // range check answers without a fetch); a row broadcast hands slot j's offset
-// to its quarter. The next batch's ids are loaded behind the gathers. Each
-// lane adds its item's slots in slot order from zero (ACCUM: from the running
-// row) and a switched-off lane adds nothing: the chain of gspmm_sum_kernel,
-// the same bits. Running rows as in the pair kernel, one store per quarter.
+// to its quarter. Each lane adds its item's slots in slot order from zero
+// (ACCUM: from the running row) and a switched-off lane adds nothing: the
+// chain of gspmm_sum_kernel, the same bits.
+// A wave's round trips other than its gathers are kept off its critical path
+// (DESIGN.md §4.1 "Column halves", the wave schedule): the nine item records
+// come in one scalar trip; the first ids leave ahead of the running row; the
+// next batch's ids are loaded behind the gathers and looked at only after the
+// batch's adds; the four rows leave in one store. Exactly 64 VGPRs (8 waves
+// per SIMD): the kernel is compiled for that occupancy, check the resource
+// usage for scratch after any change.
 template <int DEPTH, bool ACCUM>
-__global__ __launch_bounds__(256) void gspmm_items_columns_kernel(
-    int64_t num_items, int64_t ldu, uint32_t table_bytes,
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void
+gspmm_items_columns_kernel(
+    int64_t num_items, int64_t ldu, uint32_t table_bytes, uint32_t out_bytes,
     const int32_t* __restrict__ indices, const float* __restrict__ ufeat,
     float* __restrict__ out, const int32_t* __restrict__ item_rows,
     const int64_t* __restrict__ item_ptr) {
   static_assert(DEPTH >= 1 && DEPTH <= 16, "a batch's ids are one 16-lane row");
   typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-  constexpr int64_t F = 128;
   constexpr uint32_t kOff = 0xfffffc00u;  // + any lane offset: past every gated table
   const int lane = threadIdx.x & 63;
   const int q = lane >> 4, ql = lane & 15;
@@ -505,13 +511,32 @@ __global__ __launch_bounds__(256) void gspmm_items_columns_kernel(
       __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
   const int64_t i0 = wave * 4;
   if (i0 >= num_items) return;
-  // quarter t: slots [p[t], p[t + 1]) into row r[t]; none past the last item
+  // quarter t: slots [p[t], p[t + 1]) into row r[t]
   int64_t p[5];
   int64_t r[4];
+  if (i0 + 4 <= num_items) {  // uniform: every wave but, at most, the launch's last
+    // the nine records in one scalar round trip: wide loads (the arrays are
+    // only element-aligned) with nothing between them to wait for
+    typedef int32_t i32x4 __attribute__((ext_vector_type(4)));
+    typedef int64_t i64x4 __attribute__((ext_vector_type(4)));
+    typedef i32x4 i32x4_a4 __attribute__((aligned(4)));
+    typedef i64x4 i64x4_a8 __attribute__((aligned(8)));
+    const i32x4 rr = *reinterpret_cast<const i32x4_a4*>(item_rows + i0);
+    const i64x4 pp = *reinterpret_cast<const i64x4_a8*>(item_ptr + i0);
+    p[4] = item_ptr[i0 + 4];
 #pragma unroll
-  for (int t = 0; t < 5; ++t) p[t] = item_ptr[i0 + t < num_items ? i0 + t : num_items];
+    for (int t = 0; t < 4; ++t) {
+      p[t] = pp[t];
+      r[t] = rr[t];
+    }
+  } else {
+    // the last wave: none past the last item (a dead quarter has no slots and
+    // the last item's row)
 #pragma unroll
-  for (int t = 0; t < 4; ++t) r[t] = item_rows[i0 + t < num_items ? i0 + t : num_items - 1];
+    for (int t = 0; t < 5; ++t) p[t] = item_ptr[i0 + t < num_items ? i0 + t : num_items];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) r[t] = item_rows[i0 + t < num_items ? i0 + t : num_items - 1];
+  }
   int n[4], rel[4];
 #pragma unroll
   for (int t = 0; t < 4; ++t) {
@@ -522,28 +547,54 @@ __global__ __launch_bounds__(256) void gspmm_items_columns_kernel(
   const int nmax = max(max(n[0], n[1]), max(n[2], n[3]));
   const int my_n = q == 0 ? n[0] : (q == 1 ? n[1] : (q == 2 ? n[2] : n[3]));
   const int my_rel = q == 0 ? rel[0] : (q == 1 ? rel[1] : (q == 2 ? rel[2] : rel[3]));
-  const int64_t my_row = q == 0 ? r[0] : (q == 1 ? r[1] : (q == 2 ? r[2] : r[3]));
-  const bool owns = i0 + q < num_items;
-  const int32_t* __restrict__ idx = indices + p[0];
   const uint32_t ld4 = static_cast<uint32_t>(ldu) * 4u;
   const uint32_t lane_off = static_cast<uint32_t>(half) * 256u + static_cast<uint32_t>(ql) * 16u;
   const __amdgpu_buffer_rsrc_t table = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<float*>(ufeat), 0, static_cast<int>(table_bytes), 0x00020000);
-  const int64_t f0 = int64_t(half) * 64 + int64_t(ql) * 4;
+  // the wave's slots behind a descriptor: a 32-bit offset per id load
+  const __amdgpu_buffer_rsrc_t slots = __builtin_amdgcn_make_buffer_rsrc(
+      const_cast<int32_t*>(indices + p[0]), 0, 0x7fffffff, 0x00020000);
+  // all of out behind one (the gate: shorter than 4 GiB): lane ln's 16 bytes
+  // of its quarter's row
+  const __amdgpu_buffer_rsrc_t rows = __builtin_amdgcn_make_buffer_rsrc(
+      out, 0, static_cast<int>(out_bytes), 0x00020000);
+  auto row_offset = [&](int ln) -> uint32_t {
+    const int t = ln >> 4;
+    const int64_t row = t == 0 ? r[0] : (t == 1 ? r[1] : (t == 2 ? r[2] : r[3]));
+    return static_cast<uint32_t>(row) * 512u + static_cast<uint32_t>(half) * 256u +
+           static_cast<uint32_t>(ln & 15) * 16u;
+  };
 
-  // this lane's share of the batch at slot k: the byte offset of the row of
-  // slot k + ql of its quarter's item. The load stays inside the wave's slots
-  // (an ended item re-reads its last id, an empty one a neighbour's).
-  auto batch_ids = [&](int k) -> uint32_t {
+  // this lane's share of the batch at slot k: the id of slot k + ql of its
+  // quarter's item, then the byte offset of that row (past the item's end:
+  // past the table). The load stays inside the wave's slots (an ended item
+  // re-reads its last id, an empty one a neighbour's), so it needs no
+  // predicate, also for a batch that does not come.
+  auto load_ids = [&](int k) -> uint32_t {
     const int s = max(min(k + ql, my_n - 1) + my_rel, 0);
-    const uint32_t id = static_cast<uint32_t>(idx[s]);
-    return k + ql < my_n ? id * ld4 : kOff;
+    return __builtin_amdgcn_raw_buffer_load_b32(slots, static_cast<uint32_t>(s) * 4u, 0, 0);
+  };
+  auto offsets = [&](uint32_t id, int k) -> uint32_t { return k + ql < my_n ? id * ld4 : kOff; };
+  // the running row, non-temporal (RP 2 of load_out). A dead quarter reads the
+  // last item's row and stores nothing.
+  auto load_row = [&]() -> f32x4 {
+    const u32x4 w = __builtin_amdgcn_raw_buffer_load_b128(rows, row_offset(lane), 0, 2);
+    return *reinterpret_cast<const f32x4*>(&w);
   };
 
   f32x4 acc = Vec<4>::zero();
-  if (ACCUM && owns) acc = load_out<4, 2>(out + my_row * F, f0);
   if (nmax > 0) {
-    uint32_t ids = batch_ids(0);
+    // the first ids leave ahead of the running row, which comes from the
+    // fabric and is not needed before the first add: the gathers wait for the
+    // ids alone. (Vector loads return in order. The barriers keep the
+    // compiler's scheduler from swapping the two; the empty asm is the first
+    // use of the ids, where the wait goes.)
+    uint32_t raw = load_ids(0);
+    __builtin_amdgcn_sched_barrier(0);
+    if (ACCUM) acc = load_row();
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile("" : "+v"(raw));
+    uint32_t ids = offsets(raw, 0);
     int k = 0;
     // every item has DEPTH slots left: every lane gathers, no predicate
 #pragma unroll 1
@@ -553,9 +604,16 @@ __global__ __launch_bounds__(256) void gspmm_items_columns_kernel(
       for (int j = 0; j < DEPTH; ++j)
         v[j] = __builtin_amdgcn_raw_buffer_load_b128(table, row_broadcast(ids, j) + lane_off, 0,
                                                      0);
-      if (k + DEPTH < nmax) ids = batch_ids(k + DEPTH);  // uniform
+      // the next batch's ids behind the gathers, not looked at before the
+      // batch's last add: each add waits for its own gather only, and the id
+      // round trip (a first touch, from the fabric) runs beside the chain
+      raw = load_ids(k + DEPTH);
+      __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int j = 0; j < DEPTH; ++j) acc += *reinterpret_cast<const f32x4*>(&v[j]);
+      __builtin_amdgcn_sched_barrier(0);
+      asm volatile("" : "+v"(raw));
+      ids = offsets(raw, k + DEPTH);
     }
     // the rest as predicated batches, every gather of a batch in flight
     // together; a lane whose item has no slot k + j gathers past the table and
@@ -570,7 +628,8 @@ __global__ __launch_bounds__(256) void gspmm_items_columns_kernel(
           v[j] = __builtin_amdgcn_raw_buffer_load_b128(table, row_broadcast(ids, j) + lane_off,
                                                        0, 0);
       }
-      if (k + DEPTH < nmax) ids = batch_ids(k + DEPTH);  // uniform
+      raw = load_ids(k + DEPTH);
+      __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int j = 0; j < DEPTH; ++j) {
         if (j < rb) {
@@ -578,13 +637,21 @@ __global__ __launch_bounds__(256) void gspmm_items_columns_kernel(
           acc = k + j < my_n ? sum : acc;
         }
       }
+      __builtin_amdgcn_sched_barrier(0);
+      asm volatile("" : "+v"(raw));
+      ids = offsets(raw, k + DEPTH);
     }
+  } else if (ACCUM) {
+    acc = load_row();
   }
-  // one store per quarter: the row of a store is uniform, as store_out's
-  // descriptor has to be
-#pragma unroll
-  for (int t = 0; t < 4; ++t)
-    if (q == t && i0 + t < num_items) store_out<4, ACCUM ? 2 : 4>(out + r[t] * F, f0, acc);
+  // one store for the wave's four rows (sc1: the lines leave the XCD's L2, RP
+  // 2 / 4 of store_out), the quarters past the last item switched off. The
+  // lane's place is worked out again from its id in the wave: held across the
+  // batches it would be the 65th register.
+  const int ln = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+  if (i0 + (ln >> 4) < num_items)
+    __builtin_amdgcn_raw_buffer_store_b128(*reinterpret_cast<const u32x4*>(&acc), rows,
+                                           row_offset(ln), 0, 16);
 }
 
 // Combine the chunk partials of each heavy row in chunk order:
@@ -793,6 +860,7 @@ struct SumLaunch {
   int64_t urows = 0;         // rows of ufeat (0: not known)
   int items_per_wave = 1;    // 2: gspmm_items_pair_kernel where it applies
   int column_parts = 1;      // 2: gspmm_items_columns_kernel where it applies
+  int64_t orows = 0;         // rows of out (0: not known)
 };
 
 // Outputs past twice the 256 MiB Infinity Cache are stored non-temporally
@@ -817,11 +885,14 @@ static inline bool items_pair_applies(const SumLaunch& a) {
 
 // Whether it takes the column-half kernel instead: the pair kernel's gate,
 // and a table that ends 1 KiB below 4 GiB (a switched-off lane's offset plus
-// its column offset must neither wrap nor fall inside the table).
+// its column offset must neither wrap nor fall inside the table), and 32-bit
+// offsets into out for the wave's one store: out shorter than 4 GiB, which
+// needs its row count.
 static inline bool items_columns_applies(const SumLaunch& a) {
   const int64_t ldu = a.ldu ? a.ldu : a.F;
   return a.column_parts == 2 && items_pair_applies(a) &&
-         a.urows * ldu * int64_t(sizeof(float)) <= int64_t(0xfffffc00u);
+         a.urows * ldu * int64_t(sizeof(float)) <= int64_t(0xfffffc00u) && a.orows > 0 &&
+         a.orows * a.F * int64_t(sizeof(float)) < (int64_t(1) << 32);
 }
 
 static inline void launch_items_columns(const SumLaunch& a, hipStream_t stream) {
@@ -836,7 +907,8 @@ static inline void launch_items_columns(const SumLaunch& a, hipStream_t stream) 
                              : gspmm_items_columns_kernel<DEPTH, false>;
   timed_launch(stream, [&] {
     hipLaunchKernelGGL(kernel, grid_1d(blocks), dim3(256), 0, stream, a.num_items, ldu,
-                       static_cast<uint32_t>(a.urows * ldu * int64_t(sizeof(float))), a.indices,
+                       static_cast<uint32_t>(a.urows * ldu * int64_t(sizeof(float))),
+                       static_cast<uint32_t>(a.orows * a.F * int64_t(sizeof(float))), a.indices,
                        a.ufeat, a.out, a.row_order, a.chunk_beg);
   });
 }

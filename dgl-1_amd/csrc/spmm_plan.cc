@@ -1072,14 +1072,12 @@ void run_planned(SpmmPlan& plan, const RunArgs& a, const Decision& d, void* work
     }
     for (size_t i = 0; i < bp.launches.size(); ++i) {
       const BlockItems& it = bp.launches[i];
-      DGLHIP_CHECK(dglhip_gspmm_items_columns_device(
-                       a.msg, it.n_items, a.F, it.rows.data<int32_t>(), it.ptr.data<int64_t>(),
-                       (i == 0 && first_writes) ? 0 : 1, bp.indices.data<int32_t>(),
-                       ev ? nullptr : erows, static_cast<const float*>(uf), d.ld, a.urows,
-                       d.items_per_wave, d.column_parts,
-                       ev ? ev : (a.msg == DGLHIP_MSG_U_MUL_E ? a.efeat : nullptr),
-                       elen, sums, s) == 0,
-                   DGLGetLastError());
+      gspmm_items_columns(a.msg, it.n_items, a.F, it.rows.data<int32_t>(), it.ptr.data<int64_t>(),
+                          (i == 0 && first_writes) ? 0 : 1, bp.indices.data<int32_t>(),
+                          ev ? nullptr : erows, static_cast<const float*>(uf), d.ld, a.urows,
+                          d.items_per_wave, d.column_parts,
+                          ev ? ev : (a.msg == DGLHIP_MSG_U_MUL_E ? a.efeat : nullptr), elen, sums,
+                          plan.num_rows(), s);
     }
     if (a.red == DGLHIP_REDUCE_MEAN) plan_div_degree_device(plan.num_rows(), a.F, plan.indptr(),
                                                             a.out, s);

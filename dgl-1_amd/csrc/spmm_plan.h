@@ -313,4 +313,15 @@ void plan_div_degree_device(int64_t R, int64_t F, const int64_t* indptr, float* 
 void plan_add_mean_device(int64_t R, int64_t F, const int64_t* indptr, const float* sums,
                           float* out, hipStream_t s);
 
+// dglhip_gspmm_items_columns_device (gspmm.hip) for a caller that knows how
+// many rows `out` has: the column-half kernel stores through one descriptor
+// over all of out, so its gate needs out's size (out_rows 0: not known, the
+// launch runs the pair kernel). Throws where the C entry returns -1.
+void gspmm_items_columns(int msg_op, int64_t num_items, int64_t feat_len, const int32_t* item_rows,
+                         const int64_t* item_ptr, int accumulate, const int32_t* indices,
+                         const int64_t* eid, const float* ufeat, int64_t ufeat_ld,
+                         int64_t ufeat_rows, int items_per_wave, int column_parts,
+                         const float* efeat, int64_t efeat_len, float* out, int64_t out_rows,
+                         hipStream_t stream);
+
 }  // namespace dglhip

@@ -902,7 +902,11 @@ int dglhip_gspmm_items_table_device(int msg_op, int64_t num_items, int64_t feat_
  * items_per_wave 2 runs those launches four items to a wave over one half of
  * the columns, the half chosen by the workgroup's XCD label (block % 8), so
  * each XCD's L2 holds half of the source slice; it also needs ufeat to end
- * 1 KiB below 4 GiB. With items_per_wave 1 it is ignored. The same bits. */
+ * 1 KiB below 4 GiB. With items_per_wave 1 it is ignored. The same bits.
+ * That kernel stores a wave's four rows at 32-bit offsets into out, so it
+ * also needs out shorter than 4 GiB. The launch plan (dglhip_spmm_plan_run)
+ * knows out's rows and runs it; this entry does not, and runs column_parts 2
+ * as 1. */
 int dglhip_gspmm_items_columns_device(int msg_op, int64_t num_items, int64_t feat_len,
                                       const int32_t* item_rows, const int64_t* item_ptr,
                                       int accumulate, const int32_t* indices, const int64_t* eid,
