@@ -32,12 +32,12 @@
 // indices (dropout hash, attention positions) stay the CSR's.
 //
 // Dropout mask: keep(k, h) = hash(seed, k * H + h) >= threshold, a stateless
-// counter hash (gat_keep, gspmm_impl.h: host and device), so the backward and the host
+// counter hash (gat_keep, gspmm_rows.h: host and device), so the backward and the host
 // path reproduce it from (seed, slot, head) alone.
 
 #include <type_traits>
 
-#include "gspmm_impl.h"
+#include "gspmm_rows.h"
 
 namespace dglhip {
 

@@ -20,6 +20,12 @@
 //    weights come through the scalar cache (s_load), not VGPRs.
 //  * Rows are launched in degree-descending order (row_order) so the longest
 //    sequential chains start first and the tail is short.
+//
+// Where things live: the row primitives in gspmm_rows.h; the generic sum /
+// mean / max kernels and their dispatch in gspmm_impl.h, instantiated by
+// gspmm_inst.hip; the blocked schedule's item kernels, their gate and the
+// items entries of the C-ABI in gspmm_items.hip. This unit holds the other
+// g-SpMM entries and g-SDDMM.
 
 #include "gspmm_impl.h"
 #include "spmm_plan.h"
@@ -479,46 +485,13 @@ static bool is_accum(int reduce_op) {
   return reduce_op == DGLHIP_REDUCE_SUM_ACCUM || reduce_op == DGLHIP_REDUCE_MEAN_ACCUM;
 }
 
-// The operand checks of every g-SpMM entry point: the tables the message
-// reads are given, and an edge-feature row divides the feature row. Returns
-// the edge-feature length the kernels take (1 where the message reads none).
-static int64_t check_operands(int msg_op, int64_t feat_len, const float* ufeat,
-                              const float* efeat, int64_t efeat_len) {
-  const bool use_u = msg_op != DGLHIP_MSG_COPY_E;
-  const bool use_e = !copies_u(msg_op);
-  DGLHIP_CHECK(!use_u || ufeat, "ufeat is null");
-  DGLHIP_CHECK(!use_e || efeat, "efeat is null");
-  DGLHIP_CHECK(!use_e || (efeat_len >= 1 && feat_len % efeat_len == 0),
-               "edge feature length " << efeat_len << " must divide feat_len " << feat_len);
-  return use_e ? efeat_len : 1;
-}
-
-// a lane's vector of VEC features must not straddle padded rows: even strides only
-static void check_ufeat_ld(int64_t ufeat_ld, int64_t feat_len) {
-  DGLHIP_CHECK(ufeat_ld == 0 || ufeat_ld == feat_len || (ufeat_ld > feat_len && ufeat_ld % 2 == 0),
-               "ufeat_ld " << ufeat_ld << ": 0, feat_len, or an even width > feat_len");
-}
-
-void gspmm_items_columns(int msg_op, int64_t num_items, int64_t feat_len, const int32_t* item_rows,
-                         const int64_t* item_ptr, int accumulate, const int32_t* indices,
-                         const int64_t* eid, const float* ufeat, int64_t ufeat_ld,
-                         int64_t ufeat_rows, int items_per_wave, int column_parts,
-                         const float* efeat, int64_t efeat_len, float* out, int64_t out_rows,
-                         hipStream_t stream) {
-  DGLHIP_CHECK(msg_op >= 0 && msg_op <= 3, "unknown msg op " << msg_op);
-  DGLHIP_CHECK(num_items >= 0 && feat_len >= 0 && ufeat_rows >= 0 && out_rows >= 0,
-               "negative size");
-  DGLHIP_CHECK(items_per_wave == 1 || items_per_wave == 2,
-               "items_per_wave " << items_per_wave << ": 1 or 2");
-  DGLHIP_CHECK(column_parts == 1 || column_parts == 2,
-               "column_parts " << column_parts << ": 1 or 2");
-  if (num_items == 0 || feat_len == 0) return;
-  DGLHIP_CHECK(item_rows && item_ptr && indices && out, "null items/indices/out");
-  const int64_t elen = check_operands(msg_op, feat_len, ufeat, efeat, efeat_len);
-  check_ufeat_ld(ufeat_ld, feat_len);
+// (gspmm_rows.h) the items that gspmm_items.hip's gate leaves to the generic kernel
+void gspmm_items_one(int msg_op, int64_t num_items, int64_t feat_len, int64_t elen,
+                     const int32_t* item_rows, const int64_t* item_ptr, bool accumulate,
+                     const int32_t* indices, const int64_t* eid, const float* ufeat,
+                     int64_t ufeat_ld, const float* efeat, float* out, hipStream_t stream) {
   SumLaunch a{num_items, feat_len, elen, nullptr, indices, eid, ufeat, efeat,
-              out, item_rows, item_ptr, item_ptr + 1, accumulate != 0, false, ufeat_ld,
-              ufeat_rows, items_per_wave, items_per_wave == 2 ? column_parts : 1, out_rows};
+              out, item_rows, item_ptr, item_ptr + 1, accumulate, false, ufeat_ld};
   dispatch_sum(msg_op, false, a, stream);
 }
 
@@ -625,42 +598,6 @@ int dglhip_gspmm_chunked_device(int msg_op, int reduce_op, int64_t feat_len,
     });
   }
   API_END();
-}
-
-int dglhip_gspmm_items_columns_device(int msg_op, int64_t num_items, int64_t feat_len,
-                                      const int32_t* item_rows, const int64_t* item_ptr,
-                                      int accumulate, const int32_t* indices, const int64_t* eid,
-                                      const float* ufeat, int64_t ufeat_ld, int64_t ufeat_rows,
-                                      int items_per_wave, int column_parts, const float* efeat,
-                                      int64_t efeat_len, float* out, void* stream_) {
-  API_BEGIN();
-  // the rows of out are not among the arguments: column_parts 2 runs the pair
-  // kernel here (the same bits); the plan calls gspmm_items_columns itself
-  gspmm_items_columns(msg_op, num_items, feat_len, item_rows, item_ptr, accumulate, indices, eid,
-                      ufeat, ufeat_ld, ufeat_rows, items_per_wave, column_parts, efeat, efeat_len,
-                      out, 0, static_cast<hipStream_t>(stream_));
-  API_END();
-}
-
-int dglhip_gspmm_items_table_device(int msg_op, int64_t num_items, int64_t feat_len,
-                                    const int32_t* item_rows, const int64_t* item_ptr,
-                                    int accumulate, const int32_t* indices, const int64_t* eid,
-                                    const float* ufeat, int64_t ufeat_ld, int64_t ufeat_rows,
-                                    int items_per_wave, const float* efeat, int64_t efeat_len,
-                                    float* out, void* stream_) {
-  return dglhip_gspmm_items_columns_device(msg_op, num_items, feat_len, item_rows, item_ptr,
-                                           accumulate, indices, eid, ufeat, ufeat_ld, ufeat_rows,
-                                           items_per_wave, 1, efeat, efeat_len, out, stream_);
-}
-
-int dglhip_gspmm_items_device(int msg_op, int64_t num_items, int64_t feat_len,
-                              const int32_t* item_rows, const int64_t* item_ptr, int accumulate,
-                              const int32_t* indices, const int64_t* eid, const float* ufeat,
-                              int64_t ufeat_ld, const float* efeat, int64_t efeat_len,
-                              float* out, void* stream_) {
-  return dglhip_gspmm_items_table_device(msg_op, num_items, feat_len, item_rows, item_ptr,
-                                         accumulate, indices, eid, ufeat, ufeat_ld, 0, 1, efeat,
-                                         efeat_len, out, stream_);
 }
 
 int dglhip_gspmm_max_ranges_device(int msg_op, int64_t num_rows, int64_t feat_len,

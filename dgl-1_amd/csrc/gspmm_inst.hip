@@ -1,7 +1,8 @@
 // One (message, edge-feature layout) pair of the g-SpMM sum/mean/max kernels,
 // selected by -DGSPMM_INST_MSG=<DGLHIP_MSG_*> -DGSPMM_INST_EM=<EM_*> (Makefile).
 // Splitting the instantiations over translation units lets them compile in
-// parallel; the kernels themselves live in gspmm_impl.h.
+// parallel; the kernels themselves live in gspmm_impl.h (the blocked
+// schedule's item kernels, which have no such pair, in gspmm_items.hip).
 #include "gspmm_impl.h"
 
 namespace dglhip {

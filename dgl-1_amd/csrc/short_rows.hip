@@ -20,7 +20,7 @@
 // the results are bit-identical. MAXD = 0: rows without slots, R of them per
 // wave, stored as zeros (mean_accum: out + 0.0f; sum_accum never lists them).
 
-#include "gspmm_impl.h"
+#include "gspmm_rows.h"
 
 namespace dglhip {
 

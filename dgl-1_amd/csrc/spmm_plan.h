@@ -313,7 +313,7 @@ void plan_div_degree_device(int64_t R, int64_t F, const int64_t* indptr, float* 
 void plan_add_mean_device(int64_t R, int64_t F, const int64_t* indptr, const float* sums,
                           float* out, hipStream_t s);
 
-// dglhip_gspmm_items_columns_device (gspmm.hip) for a caller that knows how
+// dglhip_gspmm_items_columns_device (gspmm_items.hip) for a caller that knows how
 // many rows `out` has: the column-half kernel stores through one descriptor
 // over all of out, so its gate needs out's size (out_rows 0: not known, the
 // launch runs the pair kernel). Throws where the C entry returns -1.

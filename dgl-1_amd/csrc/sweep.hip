@@ -29,7 +29,7 @@
 #include <climits>
 #include <cstdlib>
 
-#include "gspmm_impl.h"
+#include "gspmm_rows.h"
 
 namespace dglhip {
 namespace {

@@ -913,6 +913,15 @@ int dglhip_gspmm_items_columns_device(int msg_op, int64_t num_items, int64_t fea
                                       const float* ufeat, int64_t ufeat_ld, int64_t ufeat_rows,
                                       int items_per_wave, int column_parts, const float* efeat,
                                       int64_t efeat_len, float* out, void* stream);
+/* Which kernel a launch of items with these operands takes: *kernel = 0 one
+ * item per wave, 1 two items per wave, 2 four items per wave over a column
+ * half (out_rows: the rows of out, 0: not known, as the entry above passes).
+ * A query over the numbers and the two addresses: nothing is dereferenced and
+ * nothing runs. The three kernels give the same bits, so this is the only
+ * place the choice shows. */
+int dglhip_gspmm_items_kernel(int msg_op, int64_t feat_len, int64_t ufeat_ld, int64_t ufeat_rows,
+                              int64_t out_rows, int items_per_wave, int column_parts,
+                              const float* ufeat, const float* out, int* kernel);
 
 /* Source-swept copy_u + sum (mean != 0: mean) of fp32 rows of feat_len = 64,
  * 128 or 256 floats over the CSR (indptr, indices), every row of out
