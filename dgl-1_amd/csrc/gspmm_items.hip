@@ -7,6 +7,8 @@
 // primitives, so this unit does not see gspmm_impl.h: a launch the gate
 // declines goes to gspmm.hip through gspmm_items_one.
 // Design notes: DESIGN.md §4.1 "Two items per wave" and "Column halves".
+#include <type_traits>
+
 #include "gspmm_rows.h"
 #include "spmm_plan.h"
 
@@ -159,6 +161,18 @@ __device__ __forceinline__ uint32_t row_broadcast(uint32_t v, int j) {
 // batch's adds; the four rows leave in one store. Exactly 64 VGPRs (8 waves
 // per SIMD): the kernel is compiled for that occupancy, check the resource
 // usage for scratch after any change.
+// A wave's ids in one trip (DESIGN.md §4.1 "Column halves", the id path): a
+// wave whose four items have at most kItemsColumnsIdsCap slots together reads
+// its slot range once, lane l slots 64c + l (coalesced dwords, up to four in
+// flight together, the running row behind them), and writes the rows' byte
+// offsets to its own region of LDS. A batch's offsets then come from one LDS
+// read in place of the vector load, same lanes, same slots: no id load per
+// batch, none behind the last one, and no vector round trip between two
+// batches. The region is the wave's alone and LDS runs a wave's operations in
+// order, so there is no workgroup barrier. A wave above the cap (the long
+// items at the head of a launch) loads its ids batch by batch.
+constexpr int kItemsColumnsIdsCap = 1024;
+
 template <int DEPTH, bool ACCUM>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void
 gspmm_items_columns_kernel(
@@ -173,9 +187,8 @@ gspmm_items_columns_kernel(
   const int q = lane >> 4, ql = lane & 15;
   const int64_t bl = block_linear();
   const int half = static_cast<int>(bl % 8) & 1;
-  const int64_t wave =
-      (bl >> 1) * (blockDim.x >> 6) +
-      __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
+  const int gw = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
+  const int64_t wave = (bl >> 1) * (blockDim.x >> 6) + gw;
   const int64_t i0 = wave * 4;
   if (i0 >= num_items) return;
   // quarter t: slots [p[t], p[t + 1]) into row r[t]
@@ -218,9 +231,12 @@ gspmm_items_columns_kernel(
   const uint32_t lane_off = static_cast<uint32_t>(half) * 256u + static_cast<uint32_t>(ql) * 16u;
   const __amdgpu_buffer_rsrc_t table = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<float*>(ufeat), 0, static_cast<int>(table_bytes), 0x00020000);
-  // the wave's slots behind a descriptor: a 32-bit offset per id load
+  // the wave's slots behind a descriptor: a 32-bit offset per id load, and a
+  // load past the wave's last slot is answered without a fetch
+  const int64_t total = p[4] - p[0];
   const __amdgpu_buffer_rsrc_t slots = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<int32_t*>(indices + p[0]), 0, 0x7fffffff, 0x00020000);
+      const_cast<int32_t*>(indices + p[0]), 0,
+      static_cast<int>(min(total * 4, int64_t(0x7fffffff))), 0x00020000);
   // all of out behind one (the gate: shorter than 4 GiB): lane ln's 16 bytes
   // of its quarter's row
   const __amdgpu_buffer_rsrc_t rows = __builtin_amdgcn_make_buffer_rsrc(
@@ -232,35 +248,92 @@ gspmm_items_columns_kernel(
            static_cast<uint32_t>(ln & 15) * 16u;
   };
 
-  // this lane's share of the batch at slot k: the id of slot k + ql of its
-  // quarter's item, then the byte offset of that row (past the item's end:
-  // past the table). The load stays inside the wave's slots (an ended item
-  // re-reads its last id, an empty one a neighbour's), so it needs no
-  // predicate, also for a batch that does not come.
-  auto load_ids = [&](int k) -> uint32_t {
-    const int s = max(min(k + ql, my_n - 1) + my_rel, 0);
-    return __builtin_amdgcn_raw_buffer_load_b32(slots, static_cast<uint32_t>(s) * 4u, 0, 0);
-  };
-  auto offsets = [&](uint32_t id, int k) -> uint32_t { return k + ql < my_n ? id * ld4 : kOff; };
   // the running row, non-temporal (RP 2 of load_out). A dead quarter reads the
   // last item's row and stores nothing.
   auto load_row = [&]() -> f32x4 {
     const u32x4 w = __builtin_amdgcn_raw_buffer_load_b128(rows, row_offset(lane), 0, 2);
     return *reinterpret_cast<const f32x4*>(&w);
   };
+  // the wave's region of LDS: the byte offsets of its slots' rows
+  __shared__ uint32_t ids_lds[4][kItemsColumnsIdsCap];
+  uint32_t* const wids = ids_lds[gw];
 
   f32x4 acc = Vec<4>::zero();
-  if (nmax > 0) {
+  // The wave's batches. PRELOADED: the wave's offsets go to LDS first and the
+  // batches read them there; otherwise a batch's ids come from memory.
+  auto batches = [&](auto preloaded) {
+    constexpr bool PRELOADED = decltype(preloaded)::value;
+    // this lane's share of the batch at slot k: the id of slot k + ql of its
+    // quarter's item (PRELOADED: the offset already), then the byte offset of
+    // that row (past the item's end: past the table). The load stays inside
+    // the wave's slots (an ended item re-reads its last id, an empty one a
+    // neighbour's), so it needs no predicate, also for a batch that does not
+    // come.
+    auto load_ids = [&](int k) -> uint32_t {
+      const int s = max(min(k + ql, my_n - 1) + my_rel, 0);
+      if constexpr (PRELOADED) return wids[s];
+      else
+        return __builtin_amdgcn_raw_buffer_load_b32(slots, static_cast<uint32_t>(s) * 4u, 0, 0);
+    };
+    auto offsets = [&](uint32_t id, int k) -> uint32_t {
+      return k + ql < my_n ? (PRELOADED ? id : id * ld4) : kOff;
+    };
     // the first ids leave ahead of the running row, which comes from the
     // fabric and is not needed before the first add: the gathers wait for the
     // ids alone. (Vector loads return in order. The barriers keep the
     // compiler's scheduler from swapping the two; the empty asm is the first
     // use of the ids, where the wait goes.)
-    uint32_t raw = load_ids(0);
-    __builtin_amdgcn_sched_barrier(0);
-    if (ACCUM) acc = load_row();
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("" : "+v"(raw));
+    uint32_t raw;
+    if constexpr (PRELOADED) {
+      // 256 slots per group of loads: lane l reads slots c + 64u + l, a load
+      // and its write behind a uniform branch, the lanes past the last slot
+      // switched off by the descriptor (load) and the predicate (write). A
+      // wave of more than 256 slots (one in fifty) goes round again.
+      const int T = static_cast<int>(total);
+      uint32_t g[4];
+      auto load_group = [&](int c) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          if (u == 0 || c + 64 * u < T)
+            g[u] = __builtin_amdgcn_raw_buffer_load_b32(
+                slots, static_cast<uint32_t>(c + 64 * u + lane) * 4u, 0, 0);
+        }
+      };
+      auto write_group = [&](int c) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          if (u == 0 || c + 64 * u < T) {
+            const int s = c + 64 * u + lane;
+            if (s < T) wids[s] = g[u] * ld4;
+          }
+        }
+      };
+      load_group(0);
+      __builtin_amdgcn_sched_barrier(0);
+      if (ACCUM) acc = load_row();
+      __builtin_amdgcn_sched_barrier(0);
+      asm volatile("" : "+v"(g[0]));
+      write_group(0);
+#pragma unroll 1
+      for (int c = 256; c < T; c += 256) {
+        load_group(c);
+        write_group(c);
+        // (vmcnt(0), as the writes have waited: said for the compiler, which
+        // cannot count loads behind uniform branches and would wait for the
+        // running row ahead of the first LDS read)
+        __builtin_amdgcn_s_waitcnt(0x0f70);
+      }
+      // the writes ahead of the reads, also for the compiler
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      raw = load_ids(0);
+    } else {
+      raw = load_ids(0);
+      __builtin_amdgcn_sched_barrier(0);
+      if (ACCUM) acc = load_row();
+      __builtin_amdgcn_sched_barrier(0);
+      asm volatile("" : "+v"(raw));
+    }
     uint32_t ids = offsets(raw, 0);
     int k = 0;
     // every item has DEPTH slots left: every lane gathers, no predicate
@@ -273,7 +346,8 @@ gspmm_items_columns_kernel(
                                                      0);
       // the next batch's ids behind the gathers, not looked at before the
       // batch's last add: each add waits for its own gather only, and the id
-      // round trip (a first touch, from the fabric) runs beside the chain
+      // round trip (a first touch, from the fabric; PRELOADED: an LDS read)
+      // runs beside the chain
       raw = load_ids(k + DEPTH);
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -305,9 +379,19 @@ gspmm_items_columns_kernel(
         }
       }
       __builtin_amdgcn_sched_barrier(0);
+      // PRELOADED: no vector load closes the batch, and the compiler cannot
+      // count gathers behind uniform branches: told here that all have landed
+      // (vmcnt(0), which the adds have waited for), it does not wait for the
+      // whole batch again ahead of each gather of the next one
+      if constexpr (PRELOADED) __builtin_amdgcn_s_waitcnt(0x0f70);
       asm volatile("" : "+v"(raw));
       ids = offsets(raw, k + DEPTH);
     }
+  };
+  if (nmax > 0) {
+    // uniform: all but the long items at the head of a launch
+    if (total <= kItemsColumnsIdsCap) batches(std::true_type{});
+    else batches(std::false_type{});
   } else if (ACCUM) {
     acc = load_row();
   }
@@ -459,6 +543,8 @@ int dglhip_gspmm_items_kernel(int msg_op, int64_t feat_len, int64_t ufeat_ld, in
                                      const_cast<float*>(out)});
   API_END();
 }
+
+int dglhip_gspmm_items_columns_ids_cap(void) { return kItemsColumnsIdsCap; }
 
 int dglhip_gspmm_items_columns_device(int msg_op, int64_t num_items, int64_t feat_len,
                                       const int32_t* item_rows, const int64_t* item_ptr,

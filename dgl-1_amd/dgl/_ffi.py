@@ -162,6 +162,7 @@ def _load():
                                                        _c_int, _vp, _c_i64, _vp, _vp]),
         "dglhip_gspmm_items_kernel": (_c_int, [_c_int, _c_i64, _c_i64, _c_i64, _c_i64, _c_int,
                                                _c_int, _vp, _vp, _vp]),
+        "dglhip_gspmm_items_columns_ids_cap": (_c_int, []),
         "dglhip_gspmm_sweep_device": (_c_int, [_c_i64, _c_i64, _vp, _vp, _vp, _vp, _vp, _c_i64,
                                                _c_i64, _c_int, _c_int, _c_int, _vp]),
         "dglhip_gspmm_sweep_stream_geometry": (_c_int, [_c_int, _c_int, _vp]),

@@ -922,6 +922,11 @@ int dglhip_gspmm_items_columns_device(int msg_op, int64_t num_items, int64_t fea
 int dglhip_gspmm_items_kernel(int msg_op, int64_t feat_len, int64_t ufeat_ld, int64_t ufeat_rows,
                               int64_t out_rows, int items_per_wave, int column_parts,
                               const float* ufeat, const float* out, int* kernel);
+/* The most slots four adjacent items (a wave of the column-half kernel) may
+ * have together for the wave to read its column ids in one trip and keep them
+ * in LDS; a wave with more loads them batch by batch. The same bits either
+ * way: tests build their boundary cases from this number. */
+int dglhip_gspmm_items_columns_ids_cap(void);
 
 /* Source-swept copy_u + sum (mean != 0: mean) of fp32 rows of feat_len = 64,
  * 128 or 256 floats over the CSR (indptr, indices), every row of out
