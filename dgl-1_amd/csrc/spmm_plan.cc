@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <climits>
 #include <cmath>
 #include <cstdlib>
@@ -870,7 +871,9 @@ void check_args(const SpmmPlan& plan, const RunArgs& a) {
   DGLHIP_CHECK(a.out != nullptr || plan.num_rows() == 0 || a.F == 0, "null out");
 }
 
-Decision decide(SpmmPlan& plan, const RunArgs& a, hipStream_t s) {
+// sweep_ok false: the schedule the run takes with the sweep off (what a run
+// whose rows the sweep's 8-byte accesses cannot take falls back to)
+Decision decide(SpmmPlan& plan, const RunArgs& a, hipStream_t s, bool sweep_ok = true) {
   Decision d;
   if (!plan.on_device()) {
     d.path = PATH_HOST;
@@ -885,9 +888,8 @@ Decision decide(SpmmPlan& plan, const RunArgs& a, hipStream_t s) {
   const int64_t ld_in = strided ? a.ldu : a.F;
   const bool fp32u = a.msg != DGLHIP_MSG_COPY_U_BF16;
   if (a.F == 0 || plan.num_rows() == 0) return d;
-  if ((a.red == DGLHIP_REDUCE_SUM || a.red == DGLHIP_REDUCE_MEAN ||
-       a.red == DGLHIP_REDUCE_SUM_ACCUM) && a.msg == DGLHIP_MSG_COPY_U &&
-      a.ufeat && !a.efeat && !strided && a.F == 128) {
+  if (sweep_ok && sumlike && a.msg == DGLHIP_MSG_COPY_U && a.ufeat && !a.efeat && !strided &&
+      a.F == 128) {
     // tables past the L2-sized blocked schedule's range: the source sweep
     // (running sums in LDS, no per-block pass over out)
     d.sw = plan.sweep(a.F * 4,
@@ -971,6 +973,16 @@ Decision decide(SpmmPlan& plan, const RunArgs& a, hipStream_t s) {
   }
   return d;
 }
+
+// The sweep kernels read ufeat and write out in 8-byte vectors (two floats
+// per lane at 128 floats): the rule of pick_vec (gspmm_impl.h). A run the
+// plan routed to the sweep whose rows are not 8-byte aligned takes the
+// schedule it would take with the sweep off; dglhip_sweep_fallbacks counts them.
+inline bool sweep_aligned(const RunArgs& a) {
+  return (reinterpret_cast<uintptr_t>(a.ufeat) | reinterpret_cast<uintptr_t>(a.out)) % 8 == 0;
+}
+
+std::atomic<int64_t> g_sweep_fallbacks{0};
 
 struct Workspace {
   char* base;
@@ -1165,7 +1177,10 @@ int64_t spmm_plan_workspace(SpmmPlan& plan, int msg, int red, int64_t F, int64_t
                         reinterpret_cast<const float*>(copies_u(msg) ? nullptr : (void*)1), elen,
                         emode, erow, nullptr, nullptr);
   if (msg == DGLHIP_MSG_COPY_E) a.ufeat = nullptr;
-  return decide(plan, a, s).total();
+  const Decision d = decide(plan, a, s);
+  // the pointers decide between the sweep and its fallback at the run
+  if (d.path == PATH_SWEEP) return std::max(d.total(), decide(plan, a, s, false).total());
+  return d.total();
 }
 
 void spmm_plan_run(SpmmPlan& plan, int msg, int red, int64_t F, const void* ufeat, int64_t ldu,
@@ -1185,7 +1200,11 @@ void spmm_plan_run(SpmmPlan& plan, int msg, int red, int64_t F, const void* ufea
                  DGLGetLastError());
     return;
   }
-  const Decision d = decide(plan, a, s);
+  Decision d = decide(plan, a, s);
+  if (d.path == PATH_SWEEP && !sweep_aligned(a)) {
+    d = decide(plan, a, s, false);
+    g_sweep_fallbacks.fetch_add(1, std::memory_order_relaxed);
+  }
   run_planned(plan, a, d, workspace, ws_bytes, s);
 }
 
@@ -1234,6 +1253,13 @@ int dglhip_set_sweep_schedule(int on, int64_t table_min, int64_t block_bytes, in
   p.accum_table_min = accum_table_min;
   p.accum_min_slots = accum_min_slots;
   p.accum_per_cu = accum_per_cu;
+  API_END();
+}
+
+int dglhip_sweep_fallbacks(int reset, int64_t* out) {
+  API_BEGIN();
+  DGLHIP_CHECK(out, "null output");
+  *out = reset ? g_sweep_fallbacks.exchange(0) : g_sweep_fallbacks.load();
   API_END();
 }
 

@@ -421,6 +421,14 @@ auto with_stream_kernel(int rows_per_wave, int mode, Fn fn) {
   }
 }
 
+// The kernels read ufeat and write out in vectors of `bytes` per lane (rows
+// are 64 lanes wide, so every row starts where the table does): pick_vec's
+// rule (gspmm_impl.h), here a precondition since a sweep has no scalar form
+// at 128 and 256 floats.
+bool rows_aligned(const float* ufeat, const float* out, int64_t bytes) {
+  return (reinterpret_cast<uintptr_t>(ufeat) | reinterpret_cast<uintptr_t>(out)) % bytes == 0;
+}
+
 template <int VEC, int RPW, bool MEAN>
 void launch_sweep(int64_t num_rows, const int64_t* indptr, const int32_t* indices,
                   const float* ufeat, float* out, const int32_t* row_order, int64_t lo,
@@ -467,6 +475,9 @@ int dglhip_gspmm_sweep_device(int64_t num_rows, int64_t feat_len, const int64_t*
                "sweep rows are 64, 128 or 256 floats, not " << feat_len);
   if (num_rows == 0) return 0;
   DGLHIP_CHECK(indptr && out && (ufeat || indices == nullptr), "null indptr/ufeat/out");
+  DGLHIP_CHECK(rows_aligned(ufeat, out, feat_len / 64 * 4),
+               "sweep rows of " << feat_len << " floats: ufeat and out aligned to "
+                                << feat_len / 64 * 4 << " bytes");
   const int rpw = rows_per_wave > 0 ? rows_per_wave : 20;
   const bool m = mean != 0;
 #define DGLHIP_SWEEP(VEC, R)                                                                 \
@@ -567,6 +578,8 @@ int dglhip_gspmm_sweep_stream_device(int64_t num_rows, int64_t waves_total,
   DGLHIP_CHECK(num_rows >= 0 && num_rows < (int64_t(1) << 31) && num_blocks >= 1, "sizes");
   DGLHIP_CHECK(mode >= 0 && mode <= 2 && per_cu >= 0, "mode " << mode << ", per_cu " << per_cu);
   if (num_rows == 0) return 0;
+  // the streamed kernels are the 128-float ones: two floats per lane
+  DGLHIP_CHECK(rows_aligned(ufeat, out, 8), "sweep rows: ufeat and out aligned to 8 bytes");
   with_stream_kernel(rows_per_wave, mode, [&](auto kern) {
   const int64_t wpl = sweep_waves_per_launch(kern, per_cu);
   DGLHIP_CHECK(waves_total % wpl == 0 && waves_total * rows_per_wave >= num_rows,

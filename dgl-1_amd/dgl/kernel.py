@@ -175,6 +175,15 @@ def sweep_barrier_expiries(reset=False):
     return int(v.value)
 
 
+def sweep_fallbacks(reset=False):
+    """Runs the plan routed to the sweep that took the sweep-off schedule
+    instead because ``ufeat`` or ``out`` was not 8-byte aligned (a view at an
+    odd float offset of its storage), since the last reset."""
+    v = ctypes.c_int64()
+    check_call(LIB.dglhip_sweep_fallbacks(1 if reset else 0, ctypes.byref(v)))
+    return int(v.value)
+
+
 def set_sweep_schedule(**changes):
     """Change the source-sweep knobs; returns the old ones (for restoring).
     A plan keeps the sweep layouts it built; the choice is made per call."""
@@ -2350,6 +2359,11 @@ def _gat_backward_t(ctx, d_ft, d_z):
     dev = ft2.device
     dout = (torch.zeros(fwd.num_rows, F, dtype=torch.float32, device=dev) if d_ft is None
             else _f32c(d_ft))
+    if dout.data_ptr() % 8:
+        # the entry reads dout's rows in 8-byte vectors and rejects others; the
+        # forward stored nothing for the two-pass backward, so a gradient that
+        # arrives as a view at an odd float offset is copied to rows of its own
+        dout = dout.clone()
     dz = None if d_z is None else _f32c(d_z)
     emap = _fwd_slot_of_bwd(adj)
     d_ft2 = torch.empty(bwd.num_rows, F, dtype=torch.float32, device=dev)

@@ -1004,6 +1004,15 @@ int dglhip_get_sweep_schedule(int* on, int64_t* table_min, int64_t* block_bytes,
  * wave that stopped waiting), synchronously; reset != 0 zeroes it after the
  * read. New design: no reference counterpart. */
 int dglhip_sweep_barrier_expiries(int reset, int64_t* out);
+/* The sweep kernels read ufeat and write out in 8-byte vectors, so both sweep
+ * entries above reject rows that are not aligned to their vector width (8
+ * bytes at 128 floats, 16 at 256). dglhip_spmm_plan_schedule and _workspace
+ * see no pointers: a run the plan routed to the sweep whose ufeat or out is
+ * not 8-byte aligned (a view at an odd float offset of its storage) takes the
+ * schedule it would take with the sweep off, and the workspace query reports
+ * the larger need of the two. This reads how many runs of this process did so
+ * since the last reset; reset != 0 zeroes the count. */
+int dglhip_sweep_fallbacks(int reset, int64_t* out);
 int dglhip_set_sweep_per_cu(int per_cu);
 /* Rows per wave the plan lays the streamed sweep out for: 19 (running sums
  * in LDS), 35 or 51 (19 in LDS, 16 or 32 more in registers: a CU holds more
