@@ -46,12 +46,6 @@ namespace dglhip {
 // batch's feature rows gathered after its attention, 3 the same kernel with
 // them gathered before it
 int g_gat_variant = 0;
-int g_gat_fwd_waves = 0;  // study knob: minimum waves per SIMD of the 8 x 16 forward (0, 5, 6)
-// study knob of the transposed backward (dglhip_set_gat_bwd_variant): bits 0-1
-// the g store (0 default, 1 non-temporal, 2 none: d_er is then not valid,
-// 3 16-B write-through stores regrouped through LDS);
-// bit 2 the kernel built for 5 waves per SIMD (96 VGPRs) instead of 4 (97)
-int g_gat_bwd_variant = 0;
 // study knob (dglhip_set_gat_logit_recompute): 1 lets
 // dglhip_gat_aggregate_logits_ranges_device recompute the sources' logits
 // from their gathered rows. Off by default: on the Reddit-shaped 8 x 16 layer
@@ -375,9 +369,8 @@ __global__ __launch_bounds__(256) void gat_logits_kernel(
 }
 
 template <int H, int VEC, bool DROP, bool SMALL, bool EARLY = false, int RP = 0,
-          bool LOGIT = false, int WPE = 1>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
-void gat_aggregate_lds_kernel(
+          bool LOGIT = false>
+__global__ __launch_bounds__(256) void gat_aggregate_lds_kernel(
     int64_t num_rows, int64_t D, const int64_t* __restrict__ row_beg,
     const int64_t* __restrict__ row_end, int accumulate, const int32_t* __restrict__ indices, const int32_t* __restrict__ row_order,
     const float* __restrict__ el, const float* __restrict__ er, const float* __restrict__ ft,
@@ -488,8 +481,8 @@ __device__ __forceinline__ float dpp_shl(float v) {
 // caller's packing): the pair's two operands sit in one 64-B run, one line
 // per slot instead of two (r05: 230M of the backward's 873M L2 requests per
 // call were these two 32-B reads)
-template <bool DROP, bool SMALL, int RP = 0, int WPE = 4, bool PACK = false>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void gat_backward_t_kernel(
+template <bool DROP, bool SMALL, int RP = 0, bool PACK = false>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void gat_backward_t_kernel(
     int64_t num_items, const int32_t* __restrict__ item_row, const int64_t* __restrict__ item_beg,
     const int64_t* __restrict__ item_end, int by_row, int accumulate,
     const int32_t* __restrict__ cols, const int64_t* __restrict__ fslot,
@@ -497,7 +490,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
     const float* __restrict__ dz, const float* __restrict__ dout, float alpha, float lo,
     float hi, int apply_exp, uint64_t seed0, const int64_t* __restrict__ seed_off, uint32_t thr,
     float scale, float* __restrict__ d_ft, float* __restrict__ d_el, float* __restrict__ g_out,
-    int64_t table_bytes, int gpol) {
+    int64_t table_bytes) {
   constexpr int H = 8, F = 128, U = 16;
   constexpr int LU = U + 4;  // LDS row stride by head: the pairs' writes (lane
                              // 8 jc + hc at hc * LU + jc) hit distinct banks
@@ -662,32 +655,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
           if (FULL || 4 * q + i < nb) elacc = elacc + gv[i];
       }
     }
-    // g at its forward slot, for d_er's sum over the CSR
-    if (gpol == 3) {
-      // 16-B write-through stores that drop the line from the XCD's L2
-      // (sc1): lane 2j + half takes heads 4 half .. 4 half + 3 of slot j
-      // from the LDS rows (already holding g by head), so the scattered
-      // partial lines stop evicting the block's dout rows
-      const int j = lane >> 1, half = lane & 1;
-      const int64_t p0 = __shfl(pf[0], 8 * (j & 7), 64), p1 = __shfl(pf[1], 8 * (j & 7), 64);
-      if (j < U && (FULL || j < nb)) {
-        const int64_t pj = j < 8 ? p0 : p1;
-        f32x4 gv;
-        gv.x = ld[(4 * half + 0) * LU + j];
-        gv.y = ld[(4 * half + 1) * LU + j];
-        gv.z = ld[(4 * half + 2) * LU + j];
-        gv.w = ld[(4 * half + 3) * LU + j];
-        float* dst = g_out + pj * H + 4 * half;
-        asm volatile("global_store_dwordx4 %0, %1, off sc1" : : "v"(dst), "v"(gv) : "memory");
-      }
-    } else {
+    // g at its forward slot, for d_er's sum over the CSR (no buffer: the
+    // caller wants no d_er, nothing is stored)
+    if (g_out) {
 #pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        if (FULL || jc + 8 * i < nb) {
-          if (gpol == 0) g_out[pf[i] * H + hc] = pg[i];
-          else if (gpol == 1) __builtin_nontemporal_store(pg[i], g_out + pf[i] * H + hc);
-        }
-      }
+      for (int i = 0; i < 2; ++i)
+        if (FULL || jc + 8 * i < nb) g_out[pf[i] * H + hc] = pg[i];
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -863,26 +836,9 @@ int dglhip_gat_aggregate_logits_ranges_device(
                          clamp_hi, apply_exp, seed, seed_offset, thr, scale, out_ft, out_z,    \
                          attn_out, attn_drop_out, tbytes, nullptr);                            \
   } while (0)
-#define DGLHIP_GATW(DD, SM, W)                                                                 \
-  hipLaunchKernelGGL((gat_aggregate_lds_kernel<8, 2, DD, SM, true, 2, false, W>),              \
-                     grid_1d(blocks), dim3(256), 0, stream, num_rows, head_dim, row_beg, row_end, \
-                     accumulate, indices, row_order, el, er, ft, alpha, clamp_lo, clamp_hi,      \
-                     apply_exp, seed, seed_offset, thr, scale, out_ft, out_z, attn_out,          \
-                     attn_drop_out, tbytes, nullptr)
-        if (!logit && g_gat_fwd_waves == 6) {
-          // study knob: at least 6 waves per SIMD (the no-dropout kernel is 81
-          // VGPRs, one over the 80 that 6 waves allow)
-          if (drop) { if (small) DGLHIP_GATW(true, true, 6); else DGLHIP_GATW(true, false, 6); }
-          else { if (small) DGLHIP_GATW(false, true, 6); else DGLHIP_GATW(false, false, 6); }
-        } else if (!logit && g_gat_fwd_waves == 5) {
-          if (drop) { if (small) DGLHIP_GATW(true, true, 5); else DGLHIP_GATW(true, false, 5); }
-          else { if (small) DGLHIP_GATW(false, true, 5); else DGLHIP_GATW(false, false, 5); }
-        } else {
-          if (drop) { if (small) DGLHIP_GATRP(true, true, 2); else DGLHIP_GATRP(true, false, 2); }
-          else { if (small) DGLHIP_GATRP(false, true, 2); else DGLHIP_GATRP(false, false, 2); }
-        }
+        if (drop) { if (small) DGLHIP_GATRP(true, true, 2); else DGLHIP_GATRP(true, false, 2); }
+        else { if (small) DGLHIP_GATRP(false, true, 2); else DGLHIP_GATRP(false, false, 2); }
 #undef DGLHIP_GATRP
-#undef DGLHIP_GATW
       });
       return 0;
     }
@@ -979,29 +935,26 @@ static int gat_backward_t_impl(
   // dout is gathered by destination v: num_rows rows of the forward CSR
   const int64_t tbytes = num_rows * num_heads * head_dim * int64_t(sizeof(float));
   const bool small = tbytes < (int64_t(1) << 31);
-  const int gpol = grad ? (g_gat_bwd_variant & 3) : 2;  // no grad buffer: nothing stored
-  const bool w5 = (g_gat_bwd_variant & 4) != 0;
   timed_launch(stream, [&] {
-#define DGLHIP_GBT_W(DD, SM, RPV, W, PK)                                                      \
-  hipLaunchKernelGGL((gat_backward_t_kernel<DD, SM, RPV, W, PK>), grid_1d(blocks), dim3(256),  \
-                     0, stream, num_items, item_row, item_beg, item_end, by_row, accumulate,    \
-                     cols, fslot, ft, el, er, dz, dout, alpha, clamp_lo, clamp_hi, apply_exp,   \
-                     seed, seed_offset, thr, scale, d_ft, d_el, grad, tbytes, gpol)
-#define DGLHIP_GBT_R(DD, SM, RPV)                                                             \
-  do {                                                                                        \
-    if (packed) DGLHIP_GBT_W(DD, SM, RPV, 4, true);                                           \
-    else if (w5) DGLHIP_GBT_W(DD, SM, RPV, 5, false);                                         \
-    else DGLHIP_GBT_W(DD, SM, RPV, 4, false);                                                 \
-  } while (0)
-#define DGLHIP_GBT(DD, SM) DGLHIP_GBT_R(DD, SM, 2)  // the running rows' cache policy: RP 2
-    if (drop) {
-      if (small) DGLHIP_GBT(true, true); else DGLHIP_GBT(true, false);
-    } else {
-      if (small) DGLHIP_GBT(false, true); else DGLHIP_GBT(false, false);
+  // RP 2: the running rows' cache policy; without grad no g is stored (the
+  // caller wants no d_er)
+#define DGLHIP_GBT(DD, SM, PK)                                                                \
+  hipLaunchKernelGGL((gat_backward_t_kernel<DD, SM, 2, PK>), grid_1d(blocks), dim3(256), 0,    \
+                     stream, num_items, item_row, item_beg, item_end, by_row, accumulate,      \
+                     cols, fslot, ft, el, er, dz, dout, alpha, clamp_lo, clamp_hi, apply_exp,  \
+                     seed, seed_offset, thr, scale, d_ft, d_el, grad, tbytes)
+    const int shape = (drop ? 4 : 0) | (small ? 2 : 0) | (packed ? 1 : 0);
+    switch (shape) {
+      case 0: DGLHIP_GBT(false, false, false); break;
+      case 1: DGLHIP_GBT(false, false, true); break;
+      case 2: DGLHIP_GBT(false, true, false); break;
+      case 3: DGLHIP_GBT(false, true, true); break;
+      case 4: DGLHIP_GBT(true, false, false); break;
+      case 5: DGLHIP_GBT(true, false, true); break;
+      case 6: DGLHIP_GBT(true, true, false); break;
+      default: DGLHIP_GBT(true, true, true); break;
     }
 #undef DGLHIP_GBT
-#undef DGLHIP_GBT_R
-#undef DGLHIP_GBT_W
   });
   API_END();
 }
@@ -1056,13 +1009,6 @@ int dglhip_set_gat_variant(int variant) {
   API_END();
 }
 
-int dglhip_set_gat_fwd_waves(int waves) {
-  API_BEGIN();
-  DGLHIP_CHECK(waves == 0 || waves == 5 || waves == 6, "forward waves per SIMD " << waves);
-  g_gat_fwd_waves = waves;
-  API_END();
-}
-
 int dglhip_set_gat_logit_recompute(int on) {
   API_BEGIN();
   g_gat_logit_on = on ? 1 : 0;
@@ -1083,13 +1029,6 @@ int dglhip_gat_logits_device(int64_t num_nodes, int64_t num_heads, int64_t head_
     hipLaunchKernelGGL(gat_logits_kernel, grid_1d((total + 255) / 256), dim3(256), 0, stream,
                        total, num_heads, head_dim, ft, attn_l, attn_r, el, er);
   });
-  API_END();
-}
-
-int dglhip_set_gat_bwd_variant(int variant) {
-  API_BEGIN();
-  DGLHIP_CHECK(variant >= 0 && variant <= 7, "unknown GAT backward variant " << variant);
-  g_gat_bwd_variant = variant;
   API_END();
 }
 

@@ -230,7 +230,7 @@ __device__ __forceinline__ void slot_reduce_scatter(float* q, int j) {
 //     of the slot's heads (8 heads at D = 16: one 32-B run per slot).
 // The pairing of lanes is the full xor butterfly's (4, 2, 1 / 2, 1 / 1), so
 // results are deterministic and equal the butterfly's bits.
-template <int NB, int UNROLL, int H, bool EPI = false, bool PRE = true>
+template <int NB, int UNROLL, int H, bool EPI = false>
 __global__ __launch_bounds__(256) void gsddmm_dot_sliced_kernel(
     int64_t num_rows, const int64_t* __restrict__ row_beg, const int64_t* __restrict__ row_end,
     const int32_t* __restrict__ row_order, const int32_t* __restrict__ indices, const int64_t* __restrict__ eid,
@@ -267,7 +267,7 @@ __global__ __launch_bounds__(256) void gsddmm_dot_sliced_kernel(
   const bool xl = EPI && epi.el != nullptr;  // the slope from the logits (wave-uniform)
 #pragma unroll
   for (int t = 0; t < T; ++t) {
-    dzv[t] = (EPI && PRE && epi.dz) ? epi.dz[row * H + lane_head(t)] : 0.0f;
+    dzv[t] = (EPI && epi.dz) ? epi.dz[row * H + lane_head(t)] : 0.0f;
     erv[t] = xl ? epi.er[row * H + lane_head(t)] : 0.0f;
   }
   // the fused row sums: lanes of slot group s each chain the values of every
@@ -295,9 +295,9 @@ __global__ __launch_bounds__(256) void gsddmm_dot_sliced_kernel(
       // behind the dot product (attention gradient: fewer serial latencies)
 #pragma unroll
       for (int t = 0; t < T; ++t) {
-        ea[u][t] = (EPI && PRE) ? epi.a[k * H + lane_head(t)] : 0.0f;
-        ew[u][t] = (EPI && PRE && epi.w) ? epi.w[k * H + lane_head(t)] : 0.0f;
-        ex[u][t] = (EPI && PRE && xl) ? epi.el[ucol[u] * H + lane_head(t)] : 0.0f;
+        ea[u][t] = EPI ? epi.a[k * H + lane_head(t)] : 0.0f;
+        ew[u][t] = (EPI && epi.w) ? epi.w[k * H + lane_head(t)] : 0.0f;
+        ex[u][t] = (EPI && xl) ? epi.el[ucol[u] * H + lane_head(t)] : 0.0f;
       }
     }
 #pragma unroll
@@ -326,13 +326,13 @@ __global__ __launch_bounds__(256) void gsddmm_dot_sliced_kernel(
 #pragma unroll
           for (int t = 0; t < (H >= 8 ? H / 8 : 1); ++t) {
             const int hh = j * (H / 8) + t;
-            sv[t] = EPI ? (PRE ? gat_epi_pre(epi, q[t], ea[u][t], keep_of(k, hh, ew[u][t]), dzv[t], xl ? ((ex[u][t] + erv[t]) > 0.0f ? 1 : 0) : -1) : gat_epi(epi, q[t], k, H, hh, row, ucol[u])) : q[t];
+            sv[t] = EPI ? gat_epi_pre(epi, q[t], ea[u][t], keep_of(k, hh, ew[u][t]), dzv[t], xl ? ((ex[u][t] + erv[t]) > 0.0f ? 1 : 0) : -1) : q[t];
             if (k < end) out[obase + hh] = sv[t];
           }
         } else {
           constexpr int DUP = H >= 8 ? 1 : 8 / H;  // lanes holding the same head
           const int hh = j / DUP;
-          sv[0] = EPI ? (PRE ? gat_epi_pre(epi, q[0], ea[u][0], keep_of(k, hh, ew[u][0]), dzv[0], xl ? ((ex[u][0] + erv[0]) > 0.0f ? 1 : 0) : -1) : gat_epi(epi, q[0], k, H, hh, row, ucol[u])) : q[0];
+          sv[0] = EPI ? gat_epi_pre(epi, q[0], ea[u][0], keep_of(k, hh, ew[u][0]), dzv[0], xl ? ((ex[u][0] + erv[0]) > 0.0f ? 1 : 0) : -1) : q[0];
           if (k < end && j % DUP == 0) out[obase + hh] = sv[0];
         }
       } else {
@@ -343,13 +343,13 @@ __global__ __launch_bounds__(256) void gsddmm_dot_sliced_kernel(
 #pragma unroll
           for (int t = 0; t < (NB >= LPH ? NB / LPH : 1); ++t) {
             const int hh = (r * (NB / LPH) + t) * HPB + g;
-            sv[t] = EPI ? (PRE ? gat_epi_pre(epi, p[t], ea[u][t], keep_of(k, hh, ew[u][t]), dzv[t], xl ? ((ex[u][t] + erv[t]) > 0.0f ? 1 : 0) : -1) : gat_epi(epi, p[t], k, H, hh, row, ucol[u])) : p[t];
+            sv[t] = EPI ? gat_epi_pre(epi, p[t], ea[u][t], keep_of(k, hh, ew[u][t]), dzv[t], xl ? ((ex[u][t] + erv[t]) > 0.0f ? 1 : 0) : -1) : p[t];
             if (k < end) out[obase + hh] = sv[t];
           }
         } else {
           constexpr int DUP = NB >= LPH ? 1 : LPH / NB;
           const int hh = (r / DUP) * HPB + g;
-          sv[0] = EPI ? (PRE ? gat_epi_pre(epi, p[0], ea[u][0], keep_of(k, hh, ew[u][0]), dzv[0], xl ? ((ex[u][0] + erv[0]) > 0.0f ? 1 : 0) : -1) : gat_epi(epi, p[0], k, H, hh, row, ucol[u])) : p[0];
+          sv[0] = EPI ? gat_epi_pre(epi, p[0], ea[u][0], keep_of(k, hh, ew[u][0]), dzv[0], xl ? ((ex[u][0] + erv[0]) > 0.0f ? 1 : 0) : -1) : p[0];
           if (k < end && r % DUP == 0) out[obase + hh] = sv[0];
         }
       }
@@ -448,7 +448,6 @@ __global__ __launch_bounds__(256) void gsddmm_attention_vec_kernel(
 
 // definitions of the state gspmm_impl.h declares
 Timing g_timing;
-int g_sddmm_alt = 0;
 
 // The (message, edge layout) pair of a launch: the twelve pairs the sum/mean
 // and max reducers are instantiated for (gspmm_inst.hip).
@@ -665,35 +664,23 @@ static void launch_sddmm_dot(int64_t num_rows, int64_t feat_len, int64_t num_hea
   // row sub-ranges (the source-blocked schedule) gather from L2: there the
   // shallower depth wins at F = 128 (Reddit-shaped graph, 1 / 8 / 16 heads:
   // 6.30 -> 4.89, 6.68 -> 5.69, 7.70 -> 7.07 ms per call, eid order,
-  // tools/reducer_bench.py); dglhip_set_sddmm_variant(1) swaps the two
-  const bool alt = (row_end != row_beg + 1) != ((g_sddmm_alt & 1) != 0);
-  // the GAT epilogue's per-slot operands: loaded with the slot's gathers
-  // (default), or after the dot product (dglhip_set_sddmm_variant bit 1)
-  const bool late = (g_sddmm_alt & 2) != 0;
+  // tools/reducer_bench.py)
+  const bool ranges = row_end != row_beg + 1;
   timed_launch(stream, [&] {
-#define DGLHIP_SDDMM_K2(NB, U, HH, PP)                                                     \
-  hipLaunchKernelGGL((gsddmm_dot_sliced_kernel<NB, U, HH, EPI, PP>), grid_1d(blocks),        \
+#define DGLHIP_SDDMM_K(NB, U, HH)                                                          \
+  hipLaunchKernelGGL((gsddmm_dot_sliced_kernel<NB, U, HH, EPI>), grid_1d(blocks),          \
                      dim3(256), 0, stream, num_rows, row_beg, row_end, row_order, indices, eid, \
                      lhs, rhs, out, epi)
-#define DGLHIP_SDDMM_K(NB, U, HH)                                                          \
-  do {                                                                                     \
-    if constexpr (EPI) {                                                                   \
-      if (late) DGLHIP_SDDMM_K2(NB, U, HH, false);                                         \
-      else DGLHIP_SDDMM_K2(NB, U, HH, true);                                               \
-    } else {                                                                               \
-      DGLHIP_SDDMM_K2(NB, U, HH, true);                                                    \
-    }                                                                                      \
-  } while (0)
 #define DGLHIP_SDDMM_H(NB, U, HH)                                                          \
   if (num_heads == HH) {                                                                   \
-    if (!alt) DGLHIP_SDDMM_K(NB, U, HH);                                                  \
+    if (!ranges) DGLHIP_SDDMM_K(NB, U, HH);                                                \
     else DGLHIP_SDDMM_K(NB, (U == 4 ? 2 : 2 * U), HH);                                     \
     return;                                                                                \
   }
     // default slots in flight: 8 x U. F = 128: U = 4 for every head count
     // (Reddit-shaped graph, profiles/r02/reducers_reddit.json, 16 -> 32 slots:
     // H = 1 8.92 -> 8.36 ms, H = 8 9.38 -> 8.83, H = 16 9.73 -> 9.23,
-    // H = 32 10.77 -> 10.44); dglhip_set_sddmm_variant(1) takes the other depth
+    // H = 32 10.77 -> 10.44); row ranges take the other depth
     if (sliced && nb == 1) {
       DGLHIP_SDDMM_H(1, 2, 1) DGLHIP_SDDMM_H(1, 2, 2) DGLHIP_SDDMM_H(1, 2, 4)
       DGLHIP_SDDMM_H(1, 2, 8)
@@ -720,7 +707,6 @@ static void launch_sddmm_dot(int64_t num_rows, int64_t feat_len, int64_t num_hea
                        num_rows, feat_len, num_heads, row_beg, row_end, row_order, indices, eid,
                        lhs, rhs, out, epi);
 #undef DGLHIP_SDDMM_K
-#undef DGLHIP_SDDMM_K2
 #undef DGLHIP_SDDMM_H
   });
 }
@@ -871,15 +857,6 @@ int dglhip_gat_attention_grad_device(int64_t num_rows, int64_t feat_len, int64_t
       num_rows, feat_len, num_heads, indptr, indptr ? indptr + 1 : nullptr, nullptr, indices,
       dout, ft,
       attn, attn_drop, dz, alpha, clamp_lo, clamp_hi, apply_exp, drop_scale, grad, stream);
-}
-
-int dglhip_set_sddmm_variant(int alternate) {
-  API_BEGIN();
-  // bit 0: the other depth of slots in flight; bit 1: the GAT epilogue's
-  // operands loaded after the dot product (the form before r03's prefetch)
-  DGLHIP_CHECK(alternate >= 0 && alternate <= 3, "unsupported g-SDDMM variant " << alternate);
-  g_sddmm_alt = alternate;
-  API_END();
 }
 
 int dglhip_gsddmm_attention_device(int64_t num_rows, int64_t num_heads,

@@ -368,7 +368,6 @@ __global__ __launch_bounds__(256) void gspmm_sweep_stream_kernel(
   }
 }
 
-int g_sweep_per_cu = 0;  // study knob: workgroups per CU of a launch (0: occupancy)
 // rows per wave the plan lays the streamed sweep out for (19: all in LDS;
 // 35 / 51: 16 / 32 more in registers, 124 VGPRs at 51, still 4 waves per
 // SIMD: emulated N = 8 rank 7.15 -> 6.90 ms); DGLHIP_SWEEP_ROWS
@@ -377,31 +376,26 @@ int g_sweep_rows = [] {
   const int v = e ? std::atoi(e) : 0;
   return (v == 10 || v == 19 || v == 35 || v == 51) ? v : 51;
 }();
-int g_sweep_unroll = 16;  // study knob: row gathers in flight per wave (16 or 32)
 
+// Waves of one launch: every workgroup resident at once, at most `cap`
+// workgroups per CU where cap > 0 (else what the occupancy allows)
 template <typename K>
-int64_t sweep_waves_per_launch(K kern, int cap = 0) {
+int64_t sweep_waves_per_launch(K kern, int cap) {
   int dev = 0, cus = 0, per_cu = 0;
   HIP_CALL(hipGetDevice(&dev));
   HIP_CALL(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
   HIP_CALL(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 64 * kSweepWaves, 0));
-  if (cap <= 0) cap = g_sweep_per_cu;
   if (cap > 0) per_cu = std::min(per_cu, cap);
   DGLHIP_CHECK(cus > 0 && per_cu > 0, "sweep kernel does not fit a CU");
   return int64_t(cus) * per_cu * kSweepWaves;
 }
 
-template <int RPW, int U, int RR>
-auto stream_kernel_u(int mode) {
-  return mode == 2 ? gspmm_sweep_stream_kernel<2, RPW, U, 2, RR>
-         : mode == 1 ? gspmm_sweep_stream_kernel<2, RPW, U, 1, RR>
-                     : gspmm_sweep_stream_kernel<2, RPW, U, 0, RR>;
-}
-
+// 16 row gathers in flight per wave
 template <int RPW, int RR = 0>
 auto stream_kernel(int mode) {
-  return g_sweep_unroll == 32 ? stream_kernel_u<RPW, 32, RR>(mode)
-                              : stream_kernel_u<RPW, 16, RR>(mode);
+  return mode == 2 ? gspmm_sweep_stream_kernel<2, RPW, 16, 2, RR>
+         : mode == 1 ? gspmm_sweep_stream_kernel<2, RPW, 16, 1, RR>
+                     : gspmm_sweep_stream_kernel<2, RPW, 16, 0, RR>;
 }
 
 // rows per wave of the streamed kernel: 10 or 19 in LDS; 19 in LDS plus 16
@@ -504,13 +498,6 @@ int dglhip_gspmm_sweep_device(int64_t num_rows, int64_t feat_len, const int64_t*
   API_END();
 }
 
-int dglhip_set_sweep_per_cu(int per_cu) {
-  API_BEGIN();
-  DGLHIP_CHECK(per_cu >= 0, "workgroups per CU " << per_cu);
-  g_sweep_per_cu = per_cu;
-  API_END();
-}
-
 int dglhip_set_sweep_rows(int rows_per_wave) {
   API_BEGIN();
   DGLHIP_CHECK(stream_rows_ok(rows_per_wave), "rows per wave " << rows_per_wave);
@@ -522,13 +509,6 @@ int dglhip_get_sweep_rows(int* rows_per_wave) {
   API_BEGIN();
   DGLHIP_CHECK(rows_per_wave, "null output");
   *rows_per_wave = g_sweep_rows;
-  API_END();
-}
-
-int dglhip_set_sweep_unroll(int unroll) {
-  API_BEGIN();
-  DGLHIP_CHECK(unroll == 16 || unroll == 32, "gathers in flight " << unroll);
-  g_sweep_unroll = unroll;
   API_END();
 }
 

@@ -147,7 +147,6 @@ def _load():
                                                         ctypes.c_uint64, _vp, _vp, _vp, _vp, _vp,
                                                         _vp]),
         "dglhip_set_gat_variant": (_c_int, [_c_int]),
-        "dglhip_set_gat_bwd_variant": (_c_int, [_c_int]),
         "dglhip_gat_attention_grad_device": (_c_int, [_c_i64, _c_i64, _c_i64, _vp, _vp, _vp, _vp,
                                                       _vp, _vp, _vp, ctypes.c_float,
                                                       ctypes.c_float, ctypes.c_float, _c_int,
@@ -166,7 +165,6 @@ def _load():
         "dglhip_gspmm_sweep_device": (_c_int, [_c_i64, _c_i64, _vp, _vp, _vp, _vp, _vp, _c_i64,
                                                _c_i64, _c_int, _c_int, _c_int, _vp]),
         "dglhip_gspmm_sweep_stream_geometry": (_c_int, [_c_int, _c_int, _vp]),
-        "dglhip_set_sweep_per_cu": (_c_int, [_c_int]),
         "dglhip_sweep_barrier_expiries": (_c_int, [_c_int, _vp]),
         "dglhip_sweep_fallbacks": (_c_int, [_c_int, _vp]),
         "dglhip_set_sweep_rows": (_c_int, [_c_int]),
@@ -174,8 +172,6 @@ def _load():
         "dglhip_set_sweep_schedule": (_c_int, [_c_int, _c_i64, _c_i64, _c_int, _c_int, _c_i64,
                                                _c_i64, _c_int]),
         "dglhip_get_sweep_schedule": (_c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-        "dglhip_set_gat_fwd_waves": (_c_int, [_c_int]),
-        "dglhip_set_sweep_unroll": (_c_int, [_c_int]),
         "dglhip_gspmm_sweep_stream_device": (_c_int, [_c_i64, _c_i64, _vp, _vp, _c_int, _vp, _vp,
                                                       _vp, _vp, _vp, _c_int, _c_int, _c_int, _vp,
                                                       _c_i64, _c_int, _c_int, _vp]),
@@ -205,7 +201,6 @@ def _load():
                                         _vp, _c_int]),
         "dglhip_timing_enable": (_c_int, [_c_int]),
         "dglhip_gspmm_resident_waves": (_c_int, [_c_int, ctypes.POINTER(_c_i64)]),
-        "dglhip_set_sddmm_variant": (_c_int, [_c_int]),
         "dglhip_gspmm_short_rows_device": (_c_int, [_c_int, _c_int, _c_i64, _c_i64, _c_i64,
                                                     _c_i64, _vp, _vp, _vp, _vp, _vp, _c_i64, _vp]),
         "dglhip_gspmm_strided_device": (_c_int, [_c_int, _c_int, _c_i64, _c_i64, _c_i64, _vp,

@@ -1420,14 +1420,6 @@ def gspmm_ranges(msg, beg, end, accumulate, indices, out, ufeat=None, efeat=None
     return out
 
 
-def set_sddmm_variant(alternate):
-    """Study knob for the sliced g-SDDMM dot: bit 0 runs it at its
-    alternative depth of slots in flight, bit 1 loads the GAT epilogue's
-    per-slot operands after the dot product instead of with the slot's
-    gathers; 0 (default) neither. Same bits."""
-    check_call(LIB.dglhip_set_sddmm_variant(int(alternate)))
-
-
 # per-call timing (timing_enable(per_call=True)): (start, end) event pairs
 _CALL_EVENTS = None
 
@@ -2119,20 +2111,6 @@ _GAT_SEED = {}
 _GAT_BWD = os.environ.get("DGLHIP_GAT_BWD", "auto")
 
 
-# the one-pass backward reads er and dz packed into one [rows, 2H] table
-# (dglhip_gat_backward_t_packed_device); False: two tables (study knob)
-_GAT_BWD_PACK = os.environ.get("DGLHIP_GAT_BWD_PACK", "on") != "off"
-
-
-def set_gat_bwd_pack(on):
-    """Study knob: er and dz packed into one table for the one-pass GAT
-    backward (default on); returns the old setting. Same bits."""
-    global _GAT_BWD_PACK
-    old = _GAT_BWD_PACK
-    _GAT_BWD_PACK = bool(on)
-    return old
-
-
 def set_gat_backward(policy):
     """Study / test knob for the fused GAT layer's backward: "auto" or
     "three"; returns the old policy. Same bits either way."""
@@ -2375,9 +2353,10 @@ def _gat_backward_t(ctx, d_ft, d_z):
     rest = (float(ctx.alpha), float(ctx.lo), float(ctx.hi), 1 if ctx.apply_exp else 0,
             float(ctx.p), ctx.seed, ptr(ctx.seed_off), ptr(d_ft2), ptr(d_el), ptr(g),
             _stream_of(dev))
-    if dz is not None and _GAT_BWD_PACK:
-        # er and dz side by side: a pair's two destination operands in one
-        # 64-B run, one line per slot instead of two (same bits)
+    if dz is not None:
+        # er and dz side by side in one [rows, 2H] table: a pair's two
+        # destination operands in one 64-B run, one line per slot instead of
+        # two (same bits)
         erdz = torch.cat([er, dz], 1)
         tail = (ptr(ft2), ptr(el), ptr(erdz), ptr(dout)) + rest
         entry = LIB.dglhip_gat_backward_t_packed_device

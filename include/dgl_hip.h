@@ -826,10 +826,6 @@ int dglhip_gat_attention_grad_device(int64_t num_rows, int64_t feat_len, int64_t
                                      float clamp_lo, float clamp_hi, int apply_exp,
                                      float drop_scale, float* grad, void* stream);
 
-/* Study knob: 1 = the sliced g-SDDMM dot runs at its alternative depth of
- * slots in flight (16 <-> 32, or 8 -> 16 for F >= 256), 0 = the default. */
-int dglhip_set_sddmm_variant(int alternate);
-
 /* GAT edge attention (gat/train.py:90-96), fused u_add_v SDDMM + activation:
  *   out[eid[k], h] = clamp(act(lhs[indices[k], h] + rhs[r, h]), lo, hi),
  *   act(x) = exp(leaky_relu(x, alpha)) if apply_exp else leaky_relu(x, alpha)
@@ -964,7 +960,7 @@ int dglhip_gspmm_sweep_device(int64_t num_rows, int64_t feat_len, const int64_t*
  * feat_len 128. */
 int dglhip_gspmm_sweep_stream_geometry(int rows_per_wave, int per_cu, int64_t* waves_per_launch);
 /* The same for the kernel of a given mode (0 sum, 1 mean, 2 sum continuing
- * out) at the current dglhip_set_sweep_unroll: the geometry the launch of
+ * out): the geometry the launch of
  * dglhip_gspmm_sweep_stream_device with that mode checks its layout against
  * (the plain entry above is mode 0). */
 int dglhip_gspmm_sweep_stream_geometry_mode(int rows_per_wave, int per_cu, int mode,
@@ -975,8 +971,6 @@ int dglhip_gspmm_sweep_stream_device(int64_t num_rows, int64_t waves_total,
                                      const int64_t* indptr, const float* ufeat, float* out,
                                      int mode, int rows_per_wave, int per_cu, int* arrive,
                                      int64_t arrive_len, int lag, int max_spin, void* stream);
-/* Study knobs of the sweep kernels: workgroups per CU of a launch (0: the
- * occupancy limit) and row gathers in flight per wave (16 or 32). */
 /* The plan's source-sweep schedule (DGLHIP_PLAN_PATH_SWEEP, DESIGN.md §4.1
  * "Source sweep"): taken for copy_u sum / mean of fp32 rows of 128 floats
  * over a source-monotone CSR whose referenced source table is table_min
@@ -1013,14 +1007,12 @@ int dglhip_sweep_barrier_expiries(int reset, int64_t* out);
  * the larger need of the two. This reads how many runs of this process did so
  * since the last reset; reset != 0 zeroes the count. */
 int dglhip_sweep_fallbacks(int reset, int64_t* out);
-int dglhip_set_sweep_per_cu(int per_cu);
 /* Rows per wave the plan lays the streamed sweep out for: 19 (running sums
  * in LDS), 35 or 51 (19 in LDS, 16 or 32 more in registers: a CU holds more
  * rows, so fewer launches re-sweep the source blocks; 51 is the default), 10.
  * Process-wide; env DGLHIP_SWEEP_ROWS. Same bits at every setting. */
 int dglhip_set_sweep_rows(int rows_per_wave);
 int dglhip_get_sweep_rows(int* rows_per_wave);
-int dglhip_set_sweep_unroll(int unroll);
 
 /* The max reducer of dglhip_gspmm_device over row ranges: row r's slots are
  * [row_beg[r], row_end[r]) of the CSR (argmax slot ids stay the CSR's: k,
@@ -1179,9 +1171,6 @@ int dglhip_gat_aggregate_logits_ranges_device(
     float drop_p, uint64_t seed, const int64_t* seed_offset, float* out_ft, float* out_z,
     float* attn_out, float* attn_drop_out, void* stream);
 /* Study knob: 1 switches the recompute above on (default 0; same bits). */
-/* Study knob: the 8 x 16 fused forward (row policy 2, logits gathered)
- * compiled for at least 5 or 6 waves per SIMD (0: as the compiler allocates). */
-int dglhip_set_gat_fwd_waves(int waves);
 int dglhip_set_gat_logit_recompute(int on);
 
 /* dglhip_gat_aggregate_device over row ranges: row r's slots are
@@ -1205,11 +1194,6 @@ int dglhip_gat_aggregate_ranges_device(
  * attention computed in every lane that consumes it; 2 = once per (slot,
  * head), shared through LDS (H in {1, 2, 4, 8, 16}). Same bits. */
 int dglhip_set_gat_variant(int variant);
-
-/* Study knob for dglhip_gat_backward_t_device: the attention gradient's store
- * (0 default, 1 non-temporal, 2 none — the gradient buffer is then left
- * unwritten, so d_er is not valid: timing only). */
-int dglhip_set_gat_bwd_variant(int variant);
 
 /* The attention-dropout mask of dglhip_gat_aggregate_device: keep[i] = 1 for
  * the kept (slot, head) pairs i = k * H + h, a stateless hash of (seed, i). */

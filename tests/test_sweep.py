@@ -324,11 +324,10 @@ def test_accumulating_sweep_beside_an_occupying_kernel():
 
 def test_sweep_layout_follows_the_kernel_knobs():
     """The cached sweep layout is dealt over the waves one launch of the
-    kernel that runs holds; a gathers-in-flight or rows-per-wave knob changed
-    after the plan was built (its occupancy may differ) gets a layout of its
-    own rather than a geometry mismatch at launch: same bits at
-    16 and 32 gathers in flight and at 19, 35 and 51 rows per wave (16 / 32
-    of them in registers), sum and the accumulating mode."""
+    kernel that runs holds; a rows-per-wave knob changed after the plan was
+    built (its occupancy may differ) gets a layout of its own rather than a
+    geometry mismatch at launch: same bits at 19, 35 and 51 rows
+    per wave (16 / 32 of them in registers), sum and the accumulating mode."""
     dev = _dev()
     n_src, n_dst, m = 120_000, 12_000, 2_000_000
     rng = np.random.default_rng(41)
@@ -347,20 +346,18 @@ def test_sweep_layout_follows_the_kernel_knobs():
     check_call(LIB.dglhip_get_sweep_rows(ctypes.byref(rows0)))
     try:
         res = {}
-        for unroll, rows in ((16, 19), (32, 19), (16, 51), (16, 35), (32, 51), (16, 19)):
-            check_call(LIB.dglhip_set_sweep_unroll(unroll))
+        for rows in (19, 51, 35, 19):
             check_call(LIB.dglhip_set_sweep_rows(rows))
             out = torch.full((n_dst, 128), float("nan"), device=dev)
             kernel.gspmm_into(csr, out, h)
             acc = base.clone()
             kernel.gspmm_into(csr, acc, h, accumulate=True)
             torch.cuda.synchronize()
-            assert np.array_equal(out.cpu().numpy(), ref), (unroll, rows)
+            assert np.array_equal(out.cpu().numpy(), ref), rows
             res.setdefault("acc", acc.cpu())
-            assert torch.equal(acc.cpu(), res["acc"]), (unroll, rows)
+            assert torch.equal(acc.cpu(), res["acc"]), rows
         path, _ = csr.plan.schedule(kernel.MSG_COPY_U, kernel.RED_SUM_ACCUM, 128, 0, n_src)
         assert path == kernel.PLAN_PATH_SWEEP
     finally:
-        check_call(LIB.dglhip_set_sweep_unroll(16))
         check_call(LIB.dglhip_set_sweep_rows(rows0.value))
         kernel.set_sweep_schedule(**old)

@@ -172,11 +172,6 @@ for s in $STEPS; do
       python tools/gat_bwd_split.py parse gpurun_out/gat_plan.json gpurun_out/gsa/run_counter_collection.csv \
         gpurun_out/gsb/run_counter_collection.csv --out gpurun_out/gat_bwd_l2_split.json > /dev/null
       rc=$?; tail -2 gpurun_out/gsb.log; [ $rc -eq 0 ] || exit $rc ;;
-    gatvariants)
-      # GAT 8 x 16 fwd + bwd per backward variant (VARIANTS="0 3"), interleaved rounds
-      timeout -k 10 400 python -u tools/gat_bwd_variants.py --variants ${VARIANTS:-0} --rounds ${ROUNDS:-3} \
-        --out gpurun_out/gat_bwd_variants.json > gpurun_out/gat_bwd_variants.log 2>&1
-      rc=$?; tail -3 gpurun_out/gat_bwd_variants.log; [ $rc -eq 0 ] || exit $rc ;;
     benchlegs)
       # the N = 1 line without the PMC passes, the RMAT legs and the CPU baselines (model legs timed)
       timeout -k 10 600 python bench.py --full --no-traffic --no-rmat-leg --no-sage-rmat-leg --no-cpu-baseline \

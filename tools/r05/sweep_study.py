@@ -79,8 +79,6 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--stream", action="store_true", help="also the streamed layout kernel")
     ap.add_argument("--lag", type=int, nargs="+", default=[0, 1, 2])
-    ap.add_argument("--per-cu", type=int, default=0, help="workgroups per CU (0: occupancy)")
-    ap.add_argument("--unroll", type=int, default=16)
     ap.add_argument("--scale", type=int, default=1, help="weak-scaled graph, rank 0's rows")
     ap.add_argument("--no-cursor", action="store_true", help="skip the cursor kernel")
     args = ap.parse_args()
@@ -136,9 +134,6 @@ def main():
 
     res = {"graph": "reddit_like", "order": args.order, "rounds": []}
     layouts = {}
-    if args.per_cu:
-        check_call(LIB.dglhip_set_sweep_per_cu(args.per_cu))
-    check_call(LIB.dglhip_set_sweep_unroll(args.unroll))
     if args.stream:
         for mib in args.mib:
             for rpw in args.rpw:

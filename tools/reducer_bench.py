@@ -69,29 +69,23 @@ def main():
     # g-SDDMM dot (u_mul_e weight gradient; GAT per-head dots): per slot one
     # lhs row (the destination's, reused along the row) and one gathered rhs row
     for heads in (1, 2, 4, 8, 16, 32):
-        for alt in (0, 1):
-            for order in ("eid", "slot"):
-                if order == "slot" and alt:
-                    continue
-                kernel.set_sddmm_variant(alt)
+        for order in ("eid", "slot"):
+            kernel.gsddmm_dot(adj, h, h, E, heads, edge_order=order)
+            torch.cuda.synchronize()
+            kernel.timing_enable(True)
+            for _ in range(args.iters):
                 kernel.gsddmm_dot(adj, h, h, E, heads, edge_order=order)
-                torch.cuda.synchronize()
-                kernel.timing_enable(True)
-                for _ in range(args.iters):
-                    kernel.gsddmm_dot(adj, h, h, E, heads, edge_order=order)
-                ms, cnt = kernel.timing_read()
-                kernel.timing_enable(False)
-                kernel.set_sddmm_variant(0)
-                t = ms / args.iters  # per call (a blocked call launches several kernels)
-                byts = E * (4 * F + 4 + (8 if order == "eid" else 0) + 4 * heads) + \
-                    n * (4 * F + 8)
-                res.append({"msg": "sddmm_dot", "reduce": "heads=%d" % heads,
-                            "variant": "alternate depth" if alt else "default",
-                            "edge_order": order, "kernel_ms": round(t, 3),
-                            "edges_per_s": E / (t * 1e-3),
-                            "algorithmic_GBs": round(byts / (t * 1e-3) / 1e9, 1),
-                            "launches": cnt // args.iters, "peak_GBs": peak_of(cnt // args.iters),
-                    "frac": round(byts / (t * 1e-3) / 1e9 / peak_of(cnt // args.iters), 3)})
+            ms, cnt = kernel.timing_read()
+            kernel.timing_enable(False)
+            t = ms / args.iters  # per call (a blocked call launches several kernels)
+            byts = E * (4 * F + 4 + (8 if order == "eid" else 0) + 4 * heads) + \
+                n * (4 * F + 8)
+            res.append({"msg": "sddmm_dot", "reduce": "heads=%d" % heads,
+                        "edge_order": order, "kernel_ms": round(t, 3),
+                        "edges_per_s": E / (t * 1e-3),
+                        "algorithmic_GBs": round(byts / (t * 1e-3) / 1e9, 1),
+                        "launches": cnt // args.iters, "peak_GBs": peak_of(cnt // args.iters),
+                        "frac": round(byts / (t * 1e-3) / 1e9 / peak_of(cnt // args.iters), 3)})
     # GAT edge attention (fused u_add_v -> leaky_relu -> exp), 8 heads
     a1 = torch.rand(n, 8, device=dev)
     a2 = torch.rand(n, 8, device=dev)
