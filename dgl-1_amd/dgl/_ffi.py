@@ -256,6 +256,18 @@ def _load():
         "dglhip_neighbor_sample_host": (_c_int, [_c_i64, _c_i64, _vp, _vp, _vp, _c_int, _vp,
                                                  _c_i64, _c_int, _c_i64, _c_u64, _vp]),
         "dglhip_neighbor_sample_host_fetch": (_c_int, [_c_i64, _c_i64] + [_vp] * 5),
+        "dglhip_sample_neglog": (ctypes.c_double, [_c_u64]),
+        "dglhip_sample_weighted_key": (_c_u64, [_c_u64, _c_i64, _c_i64, ctypes.c_float]),
+        "dglhip_neighbor_sample_hop_device_weighted": (_c_int, [_c_i64, _c_i64, _vp, _vp, _vp, _vp,
+                                                                _c_i64, _c_int, _c_i64, _c_u64,
+                                                                _vp, _vp, _c_i64, _vp, _vp]),
+        "dglhip_neighbor_sample_final_device_weighted": (_c_int, [_c_i64, _c_i64, _vp, _vp, _vp,
+                                                                  _vp, _c_int, _c_int, _c_i64,
+                                                                  _c_u64, _vp, _c_i64, _c_i64] +
+                                                         [_vp] * 6 + [_c_i64, _vp]),
+        "dglhip_neighbor_sample_host_weighted": (_c_int, [_c_i64, _c_i64, _vp, _vp, _vp, _vp,
+                                                          _c_int, _vp, _c_i64, _c_int, _c_i64,
+                                                          _c_u64, _vp]),
         "dglhip_xent_workspace_floats": (_c_int, []),
         "dglhip_xent_fwd_device": (_c_int, [_c_i64, _c_i64, _vp, _c_i64, _vp, _vp, _vp, _vp, _vp]),
         "dglhip_xent_bwd_device": (_c_int, [_c_i64, _c_i64, _vp, _c_i64, _vp, _vp, _vp, _vp,

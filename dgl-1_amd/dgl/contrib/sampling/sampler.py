@@ -4,10 +4,11 @@
 sampled multi-hop neighbourhood as a :class:`~dgl.subgraph.DGLSubGraph` plus a
 dict of auxiliary data. Seeds on the host go to the native sampler, as in the
 reference. Seeds given as a tensor on a ROCm device are sampled there by the
-HIP kernels of csrc/neighbor_sample.hip: the subgraph's ids and structure stay
-on the device, ``copy_from_parent`` gathers there and message passing over the
-subgraph needs no native index. A ``seed`` makes every batch reproducible on
-either route (the stateless rule of csrc/sample_key.h).
+HIP kernels of csrc/neighbor_sample.hip, uniformly or by ``node_prob``: the
+subgraph's ids and structure stay on the device, ``copy_from_parent`` gathers
+there and message passing over the subgraph needs no native index. A ``seed``
+makes every batch reproducible on either route (the stateless rules of
+csrc/sample_key.h).
 """
 from __future__ import absolute_import
 
@@ -17,6 +18,7 @@ import threading
 import torch
 
 from ... import utils
+from ...graph_index import NodeProb
 from ...subgraph import DGLSubGraph
 
 __all__ = ["NeighborSampler"]
@@ -32,8 +34,9 @@ class NSSubgraphLoader(object):
                  return_seed_id=False, seed=None):
         if not g._graph.is_readonly():
             raise NotImplementedError("subgraph loader only support read-only graphs.")
-        if node_prob is not None and node_prob.shape[0] != g.number_of_nodes():
-            raise ValueError("node_prob needs one sampling probability per node")
+        if node_prob is not None:
+            # checked and converted once, not per batch; uploaded once per device
+            node_prob = NodeProb(node_prob, g.number_of_nodes())
         self._g = g
         self._args = (expand_factor, num_hops, neighbor_type, node_prob)
         self._batch_size = int(batch_size)
@@ -176,8 +179,19 @@ def NeighborSampler(g, batch_size, expand_factor, num_hops=1, neighbor_type="in"
     num_hops : int
     neighbor_type : 'in' or 'out'
         Follow in-edges (towards predecessors) or out-edges.
-    node_prob : None
-        Only uniform sampling is supported.
+    node_prob : tensor, optional
+        One finite sampling weight >= 0 per node of ``g`` (any real dtype, on
+        the host or a device; anything else raises DGLError). A vertex with
+        more than ``expand_factor`` neighbours keeps ``expand_factor`` of
+        them drawn without replacement, each draw proportional to the
+        neighbour's weight; shorter neighbour lists are kept whole whatever
+        the weights. The weights are converted to float32 once and moved to
+        the seeds' device once. A neighbour of weight zero (or below
+        float32's normal range) is taken only when fewer than
+        ``expand_factor`` neighbours carry weight. Needs ``seed`` or seeds on
+        a device: the native sampler has no weighted draw
+        (NotImplementedError). All-ones weights are uniform in law but do not
+        reproduce the batches of ``node_prob=None``: the keys differ.
     seed_nodes : ids, optional
         All nodes when None. A tensor on a ROCm device selects the device
         route: sampling runs there and the subgraph's ids, its structure and

@@ -16,6 +16,7 @@ SUBGRAPH_CHUNK = 512  # DGLHIP_SUBGRAPH_CHUNK: slots per item of the subgraph wa
 LINE_GRAPH_TILE = 256  # DGLHIP_LINE_GRAPH_TILE: candidates per work unit
 TRAVERSAL_CHUNK = 512  # DGLHIP_TRAVERSAL_CHUNK: slots per item of a level's walk
 SAMPLE_REG_SLOTS = 256  # DGLHIP_SAMPLE_REG_SLOTS: the longest row selected from registers
+SAMPLE_LDS_SLOTS = 1024  # DGLHIP_SAMPLE_LDS_SLOTS: the longest weighted row staged in LDS
 _TRAVERSE_BFS, _TRAVERSE_TOPOLOGICAL = 0, 1
 _U64 = (1 << 64) - 1
 
@@ -280,21 +281,25 @@ def topological_frontiers(csr, opposite):
     return queue, loop.sections
 
 
-# Uniform neighbour sampling (csrc/neighbor_sample.hip, neighbor_sample_host.cc)
+# Neighbour sampling, uniform and weighted (csrc/neighbor_sample.hip, neighbor_sample_host.cc)
 def sample_mix(z):
     """The hash of the sampling rule (csrc/sample_key.h) of the integer ``z``
     taken modulo 2^64."""
     return int(LIB.dglhip_sample_mix(int(z) & _U64))
 
 
-def _neighbor_sample_host(csr, seeds, num_hops, k, seed, in_dir):
+def _neighbor_sample_host(csr, seeds, num_hops, k, seed, in_dir, node_weight):
     seeds = seeds.cpu()
     N, nnz = csr.num_rows, csr.nnz
     sizes = torch.zeros(2, dtype=torch.int64)
-    check_call(LIB.dglhip_neighbor_sample_host(
-        N, nnz, ptr(csr.indptr), ptr(csr.indices) if nnz else None,
-        ptr(csr.eid) if nnz else None, int(in_dir), ptr(seeds) if seeds.numel() else None,
-        seeds.numel(), num_hops, k, seed, ptr(sizes)))
+    graph = (N, nnz, ptr(csr.indptr), ptr(csr.indices) if nnz else None,
+             ptr(csr.eid) if nnz else None)
+    draw = (int(in_dir), ptr(seeds) if seeds.numel() else None, seeds.numel(), num_hops, k, seed,
+            ptr(sizes))
+    if node_weight is None:
+        check_call(LIB.dglhip_neighbor_sample_host(*(graph + draw)))
+    else:
+        check_call(LIB.dglhip_neighbor_sample_host_weighted(*(graph + (ptr(node_weight),) + draw)))
     nv, m = sizes.tolist()
     nodes = torch.empty(2, nv, dtype=torch.int64)
     edges = torch.empty(3, m, dtype=torch.int64)
@@ -303,7 +308,23 @@ def _neighbor_sample_host(csr, seeds, num_hops, k, seed, in_dir):
     return nodes[0], nodes[1], edges[0], edges[1], edges[2]
 
 
-def neighbor_sample(csr, seeds, num_hops, k, seed, in_dir=True, timings=None):
+def _node_weight(node_weight, csr):
+    """``node_weight`` as the weighted entry points read it, or DGLError."""
+    if not isinstance(node_weight, torch.Tensor):
+        raise DGLError("node_weight must be a tensor, got %s" % type(node_weight).__name__)
+    if node_weight.dtype != torch.float32:
+        raise DGLError("node_weight must be float32, got %s" % node_weight.dtype)
+    if node_weight.dim() != 1 or node_weight.numel() != csr.num_rows:
+        raise DGLError("node_weight needs one entry per node (%d), got shape %s"
+                       % (csr.num_rows, tuple(node_weight.shape)))
+    if node_weight.device != csr.device:
+        raise DGLError("node_weight is on %s, the graph on %s" % (node_weight.device, csr.device))
+    if not node_weight.is_contiguous():
+        raise DGLError("node_weight must be contiguous")
+    return node_weight.detach()
+
+
+def neighbor_sample(csr, seeds, num_hops, k, seed, in_dir=True, timings=None, node_weight=None):
     """The ``num_hops``-hop neighbourhood of the int64 ids ``seeds`` sampled
     at fan-out ``k`` over ``csr`` (rows = the vertex expanded:
     ``SparseAdj.fwd`` with ``in_dir``, ``.bwd`` without) by the stateless rule
@@ -320,14 +341,25 @@ def neighbor_sample(csr, seeds, num_hops, k, seed, in_dir=True, timings=None):
     On a device there is one host read for the seeds and one per hop, so it
     cannot run while the current stream is being captured. A seed outside the
     graph raises DGLError. ``timings`` (a dict) receives device events around
-    the hop loop and the final stage."""
+    the hop loop and the final stage.
+
+    ``node_weight`` (a contiguous float32 tensor of ``csr.num_rows`` entries on
+    the device of ``csr``; anything else raises DGLError) selects the weighted
+    rule of csrc/sample_key.h: a row longer than ``k`` keeps ``k`` slots drawn
+    without replacement, each draw proportional to the weight of the slot's
+    neighbour. A weight that is not positive, normal and finite counts as no
+    weight: such slots are taken only when fewer than ``k`` slots of the row
+    carry weight, first positions first. All-ones weights are uniform in law
+    but do not reproduce the sample of ``node_weight=None``: the keys differ."""
     num_hops, k, seed = int(num_hops), int(k), int(seed) & _U64
     if num_hops < 0 or k < 0:
         raise DGLError("invalid sampling parameters: %d hops, fan-out %d" % (num_hops, k))
     dev = csr.device
+    if node_weight is not None:
+        node_weight = _node_weight(node_weight, csr)
     seeds = _ids(seeds)
     if dev.type != "cuda":
-        return _neighbor_sample_host(csr, seeds, num_hops, k, seed, in_dir)
+        return _neighbor_sample_host(csr, seeds, num_hops, k, seed, in_dir, node_weight)
     _refuse_capture("neighbour sampling reads every frontier's size on the host")
     seeds = seeds.to(dev)
     N, nnz, n = csr.num_rows, csr.nnz, seeds.numel()
@@ -351,9 +383,14 @@ def neighbor_sample(csr, seeds, num_hops, k, seed, in_dir=True, timings=None):
             break
         cap = min(N - nv, size * k)
         nxt = torch.empty(cap, dtype=torch.int64, device=dev)
-        check_call(LIB.dglhip_neighbor_sample_hop_device(
-            N, nnz, ptr(csr.indptr), ptr(csr.indices) if nnz else None, ptr(front), size, hop, k,
-            seed, ptr(layer), ptr(nxt) if cap else None, cap, ptr(status.words), stream))
+        graph = (N, nnz, ptr(csr.indptr), ptr(csr.indices) if nnz else None)
+        draw = (ptr(front), size, hop, k, seed, ptr(layer), ptr(nxt) if cap else None, cap,
+                ptr(status.words), stream)
+        if node_weight is None:
+            check_call(LIB.dglhip_neighbor_sample_hop_device(*(graph + draw)))
+        else:
+            check_call(LIB.dglhip_neighbor_sample_hop_device_weighted(
+                *(graph + (ptr(node_weight),) + draw)))
         new_size, _, edges, _ = status.read()
         if new_size > cap or edges > nnz - m:
             raise DGLError("device sampling: inconsistent hop (%d of %d frontier slots, %d "
@@ -367,11 +404,16 @@ def neighbor_sample(csr, seeds, num_hops, k, seed, in_dir=True, timings=None):
     out = torch.empty(3, m, dtype=torch.int64, device=dev)
     if nv:
         ws = _workspace(LIB.dglhip_neighbor_sample_workspace_bytes(N, nv), dev)
-        check_call(LIB.dglhip_neighbor_sample_final_device(
-            N, nnz, ptr(csr.indptr), ptr(csr.indices) if nnz else None,
-            ptr(csr.eid) if m else None, int(bool(in_dir)), num_hops, k, seed, ptr(layer), nv, m,
-            ptr(nodes[0]), ptr(nodes[1]), ptr(out[0]) if m else None, ptr(out[1]) if m else None,
-            ptr(out[2]) if m else None, ptr(ws), ws.numel(), stream))
+        graph = (N, nnz, ptr(csr.indptr), ptr(csr.indices) if nnz else None,
+                 ptr(csr.eid) if m else None)
+        draw = (int(bool(in_dir)), num_hops, k, seed, ptr(layer), nv, m, ptr(nodes[0]),
+                ptr(nodes[1]), ptr(out[0]) if m else None, ptr(out[1]) if m else None,
+                ptr(out[2]) if m else None, ptr(ws), ws.numel(), stream)
+        if node_weight is None:
+            check_call(LIB.dglhip_neighbor_sample_final_device(*(graph + draw)))
+        else:
+            check_call(LIB.dglhip_neighbor_sample_final_device_weighted(
+                *(graph + (ptr(node_weight),) + draw)))
     if timings is not None:
         marks[2].record()
         marks[2].synchronize()

@@ -25,10 +25,44 @@ import torch
 from . import _ffi, kernel
 from .base import DGLError
 
-__all__ = ["GraphIndex", "SubgraphIndex", "create_graph_index", "disjoint_union",
+__all__ = ["GraphIndex", "SubgraphIndex", "NodeProb", "create_graph_index", "disjoint_union",
            "disjoint_partition", "map_to_subgraph_nid"]
 
 _CAPI = _ffi.CAPINamespace("graph_index")
+
+
+class NodeProb(object):
+    """The ``node_prob`` of weighted neighbour sampling, checked once: one
+    finite entry >= 0 per node (else DGLError), kept as float32 where it was
+    given and copied to a device the first time seeds on it are sampled."""
+
+    def __init__(self, node_prob, num_nodes):
+        if isinstance(node_prob, NodeProb):
+            node_prob = node_prob._on[0]
+        if not isinstance(node_prob, torch.Tensor):
+            try:
+                node_prob = torch.as_tensor(np.asarray(node_prob))
+            except (TypeError, ValueError, RuntimeError):
+                raise DGLError("node_prob must be a tensor of numbers")
+        if node_prob.dim() != 1 or node_prob.numel() != num_nodes:
+            raise DGLError("node_prob needs one sampling probability per node (%d), got shape %s"
+                           % (num_nodes, tuple(node_prob.shape)))
+        if node_prob.dtype == torch.bool or node_prob.is_complex():
+            raise DGLError("node_prob must hold real numbers, got %s" % node_prob.dtype)
+        w = node_prob.detach().to(torch.float32).contiguous()
+        # (after the conversion: a float64 beyond float32's range is refused too)
+        if num_nodes and not bool((torch.isfinite(w) & (w >= 0)).all()):
+            raise DGLError("node_prob must be finite and >= 0 in float32")
+        self._on = [w]
+
+    def on(self, device):
+        """The float32 weights on ``device``."""
+        device = torch.device(device)
+        for w in self._on:
+            if w.device == device:
+                return w
+        self._on.append(self._on[0].to(device))
+        return self._on[-1]
 
 
 def _as_i64(x):
@@ -354,7 +388,10 @@ class GraphIndex(object):
                           seed=None):
         """One sampled ``num_hops``-hop subgraph per seed set of the list
         ``seed_ids``: each expanded vertex keeps at most ``expand_factor`` of
-        its 'in' or 'out' neighbours, drawn uniformly.
+        its 'in' or 'out' neighbours, drawn uniformly, or with ``node_prob``
+        (one finite entry >= 0 per node, or a :class:`NodeProb`; else
+        DGLError) without replacement with each draw proportional to the
+        neighbour's entry.
 
         Seed sets on the host with ``seed`` None go to the native sampler
         (``_CAPI_DGLGraphUniformSampling*``), which draws afresh on every call.
@@ -363,11 +400,17 @@ class GraphIndex(object):
         device; subgraph ``i`` of the call is drawn under ``mix(seed + i)``,
         and a device call without a ``seed`` draws a fresh one. That route
         leaves a subgraph's ids and edge list where the seeds are. Every
-        returned index carries the layer of its nodes as ``induced_layers``."""
+        returned index carries the layer of its nodes as ``induced_layers``.
+
+        The native sampler has no weighted draw: ``node_prob`` with host seeds
+        and no ``seed`` raises NotImplementedError. With device seeds or a
+        ``seed`` the weights are checked once per call, converted to float32
+        and moved to the seeds' device (kernel.neighbor_sample's
+        ``node_weight``)."""
         if not self._readonly:
             raise NotImplementedError("neighbor sampling only supports read-only graphs.")
-        if node_prob is not None:
-            raise NotImplementedError("non-uniform neighbor sampling is not supported.")
+        if node_prob is not None and not isinstance(node_prob, NodeProb):
+            node_prob = NodeProb(node_prob, self.number_of_nodes())
         if neighbor_type not in ("in", "out"):
             raise DGLError("neighbor_type must be 'in' or 'out', got %r" % (neighbor_type,))
         if isinstance(expand_factor, bool) or not isinstance(expand_factor, (int, np.integer)):
@@ -380,6 +423,9 @@ class GraphIndex(object):
         if len(seed_ids) == 0:
             return []
         on_device = [isinstance(s, torch.Tensor) and s.is_cuda for s in seed_ids]
+        if seed is None and not any(on_device) and node_prob is not None:
+            raise NotImplementedError("the native sampler has no non-uniform draw: pass seed= "
+                                      "or give the seeds as a tensor on a ROCm device.")
         if seed is None and not any(on_device):
             return self._native_sampling([_as_i64(s) for s in seed_ids], expand_factor, num_hops,
                                          neighbor_type)
@@ -394,7 +440,8 @@ class GraphIndex(object):
             in_dir = neighbor_type == "in"
             vertices, layers, src, dst, eid = kernel.neighbor_sample(
                 adj.fwd if in_dir else adj.bwd, ids, num_hops, expand_factor,
-                kernel.sample_mix(int(seed) + i), in_dir=in_dir)
+                kernel.sample_mix(int(seed) + i), in_dir=in_dir,
+                node_weight=None if node_prob is None else node_prob.on(ctx))
             sgi = SubgraphIndex(self, vertices, eid, device_coo=(vertices.numel(), src, dst))
             sgi.induced_layers = layers
             out.append(sgi)

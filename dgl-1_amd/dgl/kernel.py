@@ -38,7 +38,8 @@ from ._ffi import LIB, check_call, ptr, stream_of as _stream_of
 from .base import DGLError
 # graph_index, the tools and the tests reach the device graph builders as kernel.<name>
 from .device_graph import (  # noqa: F401
-    SUBGRAPH_CHUNK, LINE_GRAPH_TILE, TRAVERSAL_CHUNK, SAMPLE_REG_SLOTS, _workspace,
+    SUBGRAPH_CHUNK, LINE_GRAPH_TILE, TRAVERSAL_CHUNK, SAMPLE_REG_SLOTS, SAMPLE_LDS_SLOTS,
+    _workspace,
     induced_subgraph_count, induced_subgraph_fill, induced_subgraph,
     line_graph_count, line_graph_fill, line_graph,
     bfs_frontiers, topological_frontiers, sample_mix, neighbor_sample)

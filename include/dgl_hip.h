@@ -683,6 +683,8 @@ int dglhip_traversal_level_device(int mode, int64_t num_nodes, int64_t nnz, cons
 /* during the selection; a longer one recomputes them in every pass.         */
 /* ------------------------------------------------------------------------ */
 #define DGLHIP_SAMPLE_REG_SLOTS 256
+/* The longest row whose weighted keys a wave stages in LDS (weighted calls). */
+#define DGLHIP_SAMPLE_LDS_SLOTS 1024
 /* The hash of the rule and the key of one slot (host). */
 uint64_t dglhip_sample_mix(uint64_t z);
 uint64_t dglhip_sample_key(uint64_t seed, int64_t vertex, int64_t position);
@@ -726,6 +728,49 @@ int dglhip_neighbor_sample_host(int64_t num_nodes, int64_t nnz, const int64_t* i
 int dglhip_neighbor_sample_host_fetch(int64_t num_vertices, int64_t num_edges, int64_t* vertices,
                                       int64_t* layers, int64_t* sub_src, int64_t* sub_dst,
                                       int64_t* parent_eid);
+
+/* Weighted neighbour sampling (NeighborSampler's node_prob): the reference's
+ * GetNonUniformSample (src/graph/immutable_graph.cc) as an exponential race
+ * (Efraimidis-Spirakis). With h = dglhip_sample_key(seed, v, p) and w =
+ * node_weight[neighbour of slot p] (float32, one per node), slot p has the key
+ *   bits(E / (double)w), E = dglhip_sample_neglog((h >> 11) + 1),
+ * when w is positive, normal and finite, else (zero, denormal, negative,
+ * infinity, NaN, or a neighbour outside [0, num_nodes), which is never used as
+ * an index) 0x7FF0000000000000: a weightless slot. Selection, emission order,
+ * edge counts, status words and the workspace are those of the uniform calls:
+ * a row of d <= fanout slots keeps every slot whatever the weights, a longer
+ * one the fanout smallest (key, p), so the kept slots are successive draws
+ * proportional to w without replacement and weightless slots enter only when
+ * fewer than fanout slots carry weight, first positions first. E uses integer
+ * operations and IEEE double +, -, *, / only (csrc/sample_key.h), so the
+ * device, the host twin and a numpy restatement agree bit for bit. The init,
+ * workspace_bytes and host_fetch calls above serve both routes. node_weight
+ * is a device pointer for the device calls; NULL is an error. On the device a
+ * row of up to DGLHIP_SAMPLE_REG_SLOTS slots keeps its keys in registers, one
+ * of up to DGLHIP_SAMPLE_LDS_SLOTS stages them once in the wave's 8 KB of LDS,
+ * a longer one recomputes them in eight byte-wide passes and once to emit. */
+/* -ln(m 2^-53) for m in [1, 2^53] by the rule's series, and the weighted key
+ * of one slot whose neighbour has the given weight (host). */
+double dglhip_sample_neglog(uint64_t m);
+uint64_t dglhip_sample_weighted_key(uint64_t seed, int64_t vertex, int64_t position, float weight);
+int dglhip_neighbor_sample_hop_device_weighted(int64_t num_nodes, int64_t nnz,
+                                               const int64_t* indptr, const int32_t* indices,
+                                               const float* node_weight, const int64_t* frontier,
+                                               int64_t frontier_len, int hop, int64_t fanout,
+                                               uint64_t seed, int32_t* layer, int64_t* next,
+                                               int64_t next_capacity, int64_t* status,
+                                               void* stream);
+int dglhip_neighbor_sample_final_device_weighted(
+    int64_t num_nodes, int64_t nnz, const int64_t* indptr, const int32_t* indices,
+    const int64_t* eid, const float* node_weight, int in_direction, int num_hops, int64_t fanout,
+    uint64_t seed, const int32_t* layer, int64_t num_vertices, int64_t num_edges,
+    int64_t* vertices, int64_t* layers, int64_t* sub_src, int64_t* sub_dst, int64_t* parent_eid,
+    void* workspace, int64_t workspace_bytes, void* stream);
+int dglhip_neighbor_sample_host_weighted(int64_t num_nodes, int64_t nnz, const int64_t* indptr,
+                                         const int32_t* indices, const int64_t* eid,
+                                         const float* node_weight, int in_direction,
+                                         const int64_t* seeds, int64_t num_seeds, int num_hops,
+                                         int64_t fanout, uint64_t seed, int64_t* sizes);
 
 /* ------------------------------------------------------------------------ */
 /* Weighted softmax cross-entropy over node rows (csrc/node_loss.hip): the   */
