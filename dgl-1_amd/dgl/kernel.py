@@ -1136,6 +1136,18 @@ def _f32c(t):
     return t.contiguous()
 
 
+def _operand_rows(grad, rows):
+    """``grad`` (a row per column of the adjacency) as the gradient of an
+    operand of ``rows`` rows: an operand may carry more rows than the
+    adjacency has columns (gspmm, gat_aggregate), and no edge reads those, so
+    their gradient is zero."""
+    if grad is None or grad.shape[0] == rows:
+        return grad
+    out = grad.new_zeros((rows,) + tuple(grad.shape[1:]))
+    out[:grad.shape[0]] = grad
+    return out
+
+
 def _mean_scaled(fwd, dout, padded_ok):
     """dC / deg, the mean reducer's backward ahead of the transposed product;
     with ``padded_ok`` (only the node gradient reads it) written straight into
@@ -1209,6 +1221,7 @@ class _GSpMM(torch.autograd.Function):
                                    dout, efeat2 if reads_e else None, elen if reads_e else 0, F,
                                    False, emap=_fwd_slot_of_bwd(adj) if (slot and reads_e)
                                    else None)
+                du = _operand_rows(du, ctx.ushape[0])
             if need_e:
                 rows = fwd.row_ids()
                 if msg == MSG_COPY_E:
@@ -2068,7 +2081,8 @@ class _EdgeAttention(torch.autograd.Function):
                               emap=_fwd_slot_of_bwd(adj) if ctx.slot else None)
         d_dst, _ = _run_gspmm(adj.fwd, MSG_COPY_E, RED_SUM, None, g, H, H, False,
                               emap=SLOT if ctx.slot else None)
-        return None, None, None, None, None, None, d_src, d_dst, None
+        return (None, None, None, None, None, None, _operand_rows(d_src, a_src.shape[0]), d_dst,
+                None)
 
 
 def _edge_logits(adj, a_src, a_dst, slot, tr, num_edges):
@@ -2263,7 +2277,9 @@ class _GATAggregate(torch.autograd.Function):
         F = ft2.shape[1]
         need_el, need_er, need_ft = ctx.needs_input_grad[8:11]
         d_el = d_er = d_ft2 = None
-        d_ft = torch.zeros_like(ft2) if d_ft is None else d_ft.contiguous()
+        # (fs unused: its zero gradient has the adjacency's rows, not ft's)
+        d_ft = (torch.zeros(fwd.num_rows, F, dtype=torch.float32, device=ft2.device)
+                if d_ft is None else d_ft.contiguous())
         wt = w if w is not None else a
         if need_ft:
             # (source-blocked where the transpose qualifies: _run_gspmm)
@@ -2317,7 +2333,8 @@ class _GATAggregate(torch.autograd.Function):
                 d_el = _gat_el_grad(adj, g, H)
             if need_er and d_er is None:
                 d_er, _ = _run_gspmm(fwd, MSG_COPY_E, RED_SUM, None, g, H, H, False, emap=SLOT)
-        return (None,) * 8 + (d_el, d_er, d_ft2, None, None, None)
+        return (None,) * 8 + (_operand_rows(d_el, el.shape[0]), d_er,
+                              _operand_rows(d_ft2, ft2.shape[0]), None, None, None)
 
 
 def _gat_backward_t(ctx, d_ft, d_z):
@@ -2386,8 +2403,8 @@ def _gat_backward_t(ctx, d_ft, d_z):
         check_call(LIB.dglhip_rowsum_heads8_device(fwd.num_rows, ptr(fwd.indptr),
                                                    ptr(fwd.row_order), ptr(g), ptr(d_er),
                                                    _stream_of(dev)))
-    return ((None,) * 8 + (d_el if need_el else None, d_er, d_ft2 if need_ft else None, None,
-                           None))
+    return ((None,) * 8 + (_operand_rows(d_el, el.shape[0]) if need_el else None, d_er,
+                           _operand_rows(d_ft2, ft2.shape[0]) if need_ft else None, None, None))
 
 
 # el's gradient reads the E x H attention gradient (forward slot order)
@@ -2435,7 +2452,9 @@ def gat_aggregate(adj, ft, el, er, alpha=0.2, clamp=(-10.0, 10.0), attn_drop=0.0
         z      = sum a
 
     returned as (ft_sum (R, H, D), z (R, H, 1)), differentiable in ft, el, er.
-    ft (N, H, D); el (N, H[, 1]); er (R, H[, 1]). Equals edge_attention(...,
+    ft (N, H, D); el (N, H[, 1]); er (R, H[, 1]); ft and el may carry more rows
+    than the adjacency has columns (their gradients' extra rows are zero).
+    Equals edge_attention(...,
     edge_order="slot") followed by gspmm(u_mul_e, sum) and gspmm(copy_e, sum)
     bit for bit. The dropout mask is the kernel's counter hash of (seed,
     slot, head) (gat_dropout_mask), not torch's generator; ``seed`` None draws
