@@ -1,5 +1,6 @@
 // What the device graph builders share (induced_subgraph.hip, traversal.hip,
-// neighbor_sample.hip, line_graph.hip and the item list of typed_block.hip).
+// neighbor_sample.hip, line_graph.hip, degree_buckets.hip and the item list of
+// typed_block.hip).
 // Each of them counts, scans the counts with rocPRIM, lets the caller read a
 // few status words, and fills: the workspace carving, the scan, the argument
 // checks and the wave-level and row-level device helpers of that scheme are

@@ -230,6 +230,11 @@ def _load():
                                                           _vp, _c_i64, _vp, _vp]),
         "dglhip_induced_subgraph_fill_device": (_c_int, [_c_i64, _c_i64, _c_i64] + [_vp] * 5 +
                                                 [_c_i64, _c_i64, _c_i64] + [_vp] * 4),
+        "dglhip_degree_buckets_workspace_bytes": (_c_i64, [_c_i64, _c_i64]),
+        "dglhip_degree_buckets_count_device": (_c_int, [_c_i64, _c_i64, _vp, _vp, _c_i64, _vp,
+                                                        _vp]),
+        "dglhip_degree_buckets_fill_device": (_c_int, [_c_i64, _c_i64, _vp, _vp, _vp, _c_i64,
+                                                       _c_i64, _c_i64, _c_i64] + [_vp] * 7),
         "dglhip_line_graph_workspace_bytes": (_c_i64, [_c_i64, _c_i64]),
         "dglhip_line_graph_count_device": (_c_int, [_c_i64, _c_i64] + [_vp] * 4 +
                                            [_c_int, _vp, _c_i64, _vp, _vp]),

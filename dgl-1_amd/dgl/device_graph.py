@@ -1,7 +1,8 @@
 """Graph structures built on the device (node-induced subgraph, line graph,
-BFS / topological frontiers, neighbour sampling): a count stage, one host read
-of four status words, a fill stage (csrc/induced_subgraph.hip, line_graph.hip,
-traversal.hip, neighbor_sample.hip, over csrc/compact.h). What their host
+BFS / topological frontiers, neighbour sampling, the degree buckets of a UDF
+reduce): a count stage, one host read of four status words, a fill stage
+(csrc/induced_subgraph.hip, line_graph.hip, traversal.hip, neighbor_sample.hip,
+degree_buckets.hip, over csrc/compact.h). What their host
 sides share is here once: :class:`_Status`, :func:`_workspace`, :func:`_ids`
 and :func:`_refuse_capture`. ``dgl.kernel`` re-exports the public names.
 """
@@ -17,6 +18,7 @@ LINE_GRAPH_TILE = 256  # DGLHIP_LINE_GRAPH_TILE: candidates per work unit
 TRAVERSAL_CHUNK = 512  # DGLHIP_TRAVERSAL_CHUNK: slots per item of a level's walk
 SAMPLE_REG_SLOTS = 256  # DGLHIP_SAMPLE_REG_SLOTS: the longest row selected from registers
 SAMPLE_LDS_SLOTS = 1024  # DGLHIP_SAMPLE_LDS_SLOTS: the longest weighted row staged in LDS
+BUCKET_CHUNK = 512  # DGLHIP_BUCKET_CHUNK: slots per item of the degree buckets' message copy
 _TRAVERSE_BFS, _TRAVERSE_TOPOLOGICAL = 0, 1
 _U64 = (1 << 64) - 1
 
@@ -172,6 +174,90 @@ def line_graph(csr_bwd, src, dst, backtracking):
         raise DGLError("the line graph has M = %d edges: its edge list needs %d bytes and the "
                        "device has %d free" % (m, need, free))
     return line_graph_fill(csr_bwd, src, dst, backtracking, ws, units, m)
+
+
+# Degree buckets of a UDF reduce (csrc/degree_buckets.hip)
+class DegreeBuckets(object):
+    """The degree-bucketing schedule of ``R`` receiver rows, on the device:
+    ``bucket_deg`` [nb], ``bucket_node_ptr`` [nb + 1], ``nodes`` [listed],
+    ``zero_nodes`` [R - listed], ``msg_ids`` [nnz] and ``merge_inv`` [R], all
+    int64 (include/dgl_hip.h). ``host_deg`` and ``host_node_ptr`` are the
+    bucket table as Python ints, read once when the schedule was built: a loop
+    over the buckets sizes its slices from them and waits on nothing."""
+
+    def __init__(self, R, listed, max_degree, table, rows, msg_ids, merge_inv, host_table):
+        nb = (table.numel() - 1) // 2
+        self.R, self.listed, self.max_degree = R, listed, max_degree
+        self.bucket_deg, self.bucket_node_ptr = table[:nb], table[nb:]
+        self.nodes, self.zero_nodes = rows[:listed], rows[listed:]
+        self.msg_ids, self.merge_inv = msg_ids, merge_inv
+        self.host_deg, self.host_node_ptr = host_table[:nb], host_table[nb:]
+
+    @property
+    def num_buckets(self):
+        return len(self.host_deg)
+
+
+def degree_buckets_count(csr):
+    """Stage A of :func:`degree_buckets` over the receiver-major ``csr``:
+    (workspace, [buckets, listed rows, max degree, items]), the four counts
+    read once through pinned memory."""
+    dev = csr.device
+    R, nnz = csr.num_rows, csr.nnz
+    ws = _workspace(LIB.dglhip_degree_buckets_workspace_bytes(R, nnz), dev)
+    status = _Status(dev)
+    check_call(LIB.dglhip_degree_buckets_count_device(
+        R, nnz, ptr(csr.indptr), ptr(ws), ws.numel(), ptr(status.words), _stream_of(dev)))
+    return ws, status.read()
+
+
+def degree_buckets_fill(csr, slot_msg, ws, counts):
+    """Stage B: the :class:`DegreeBuckets` of ``csr`` from the workspace and
+    the ``counts`` of stage A; the bucket table is read once through pinned
+    memory."""
+    dev = csr.device
+    R, nnz = csr.num_rows, csr.nnz
+    nb, listed, max_degree, items = counts
+    if not (0 <= listed <= R and 0 <= nb <= listed and items <= R + nnz // BUCKET_CHUNK + 1):
+        raise DGLError("degree buckets: inconsistent counts (%d buckets, %d of %d rows, %d items)"
+                       % (nb, listed, R, items))
+    table = torch.empty(2 * nb + 1, dtype=torch.int64, device=dev)
+    rows = torch.empty(R, dtype=torch.int64, device=dev)
+    msg_ids = torch.empty(nnz, dtype=torch.int64, device=dev)
+    merge_inv = torch.empty(R, dtype=torch.int64, device=dev)
+    check_call(LIB.dglhip_degree_buckets_fill_device(
+        R, nnz, ptr(csr.indptr), ptr(slot_msg), ptr(ws), ws.numel(), nb, listed, items,
+        ptr(table[:nb]) if nb else None, ptr(table[nb:]), ptr(rows[:listed]) if listed else None,
+        ptr(rows[listed:]) if listed < R else None, ptr(msg_ids) if nnz else None,
+        ptr(merge_inv) if R else None, _stream_of(dev)))
+    host = torch.empty(2 * nb + 1, dtype=torch.int64, pin_memory=True)
+    host.copy_(table, non_blocking=True)
+    torch.cuda.current_stream(dev).synchronize()
+    return DegreeBuckets(R, listed, max_degree, table, rows, msg_ids, merge_inv, host.tolist())
+
+
+def degree_buckets(csr, slot_msg=None):
+    """The degree-bucketing schedule (:class:`DegreeBuckets`) of the messages
+    held by the receiver-major ``csr`` on a ROCm device: row r = receiver r,
+    its slots in message order, slot k holding message ``slot_msg[k]`` (int64
+    on the device of ``csr``; None: message k). For the CSR that
+    ``build_csr(R, M, msg_recv, arange(M), ORDER_EID)`` makes and ``slot_msg =
+    csr.eid`` the arrays are those of ``dglhip_degree_bucketing_host`` over
+    ``msg_recv``, element for element.
+
+    Two host reads per call (the four counts, then the bucket table), so it
+    cannot run while the current stream is being captured."""
+    dev = csr.device
+    if dev.type != "cuda":
+        raise DGLError("the device route of degree bucketing needs a CSR on a ROCm device")
+    _refuse_capture("degree bucketing reads the bucket table on the host")
+    if slot_msg is not None:
+        slot_msg = _ids(slot_msg, dev)
+        if slot_msg.numel() != csr.nnz:
+            raise DGLError("degree_buckets(): %d message ids for a CSR of %d slots"
+                           % (slot_msg.numel(), csr.nnz))
+    ws, counts = degree_buckets_count(csr)
+    return degree_buckets_fill(csr, slot_msg, ws, counts)
 
 
 # BFS and topological frontiers (csrc/traversal.hip)

@@ -39,9 +39,10 @@ from .base import DGLError
 # graph_index, the tools and the tests reach the device graph builders as kernel.<name>
 from .device_graph import (  # noqa: F401
     SUBGRAPH_CHUNK, LINE_GRAPH_TILE, TRAVERSAL_CHUNK, SAMPLE_REG_SLOTS, SAMPLE_LDS_SLOTS,
-    _workspace,
+    BUCKET_CHUNK, _workspace,
     induced_subgraph_count, induced_subgraph_fill, induced_subgraph,
     line_graph_count, line_graph_fill, line_graph,
+    DegreeBuckets, degree_buckets_count, degree_buckets_fill, degree_buckets,
     bfs_frontiers, topological_frontiers, sample_mix, neighbor_sample)
 
 __all__ = ["CSR", "SparseAdj", "build_csr", "gspmm", "gsddmm_dot",

@@ -107,8 +107,9 @@ def _all_nodes(g, recv_nodes):
 
 
 def _bucket_fn(g, rfunc, recv_nodes, msg_dst):
+    # (recv_nodes None = every node: the device route never lists them)
     return var.FUNC(lambda msgs: degree_bucketing.bucket_reduce(
-        g, rfunc, _all_nodes(g, recv_nodes), msg_dst, msgs, g._node_frame), "reduce_func")
+        g, rfunc, recv_nodes, msg_dst, msgs, g._node_frame), "reduce_func")
 
 
 def _builtin_over_messages(g, rfn, msgs, inc, recv_nodes, msg_dst, out, msg_eid=None):
@@ -124,7 +125,7 @@ def _builtin_over_messages(g, rfn, msgs, inc, recv_nodes, msg_dst, out, msg_eid=
     ir.CALL_(var.FUNC(check, "check_msg"))
     m = ir.READ_COL(msgs, var.STR(rfn.msg_field))
     fallback = var.FUNC(lambda mt: degree_bucketing.bucket_reduce(
-        g, rfn, _all_nodes(g, recv_nodes), msg_dst,
+        g, rfn, recv_nodes, msg_dst,
         {rfn.msg_field: mt if msg_eid is None else mt[msg_eid.to(mt.device)]},
         g._node_frame)[rfn.out_field],
         "bucket_" + rfn.name)

@@ -69,11 +69,17 @@ class EdgeBatch(object):
 
 
 class NodeBatch(object):
-    """A batch of nodes: ``data`` features and, in reduce UDFs, ``mailbox``."""
+    """A batch of nodes: ``data`` features and, in reduce UDFs, ``mailbox``.
 
-    def __init__(self, g, nodes, data, msgs=None):
+    ``nodes`` is the id tensor, or a zero-argument callable that gives it
+    (with ``batch_size`` the number of ids): it is called on the first
+    :meth:`nodes` and its result kept, so ids that live on a device are copied
+    to the host only for a UDF that asks for them."""
+
+    def __init__(self, g, nodes, data, msgs=None, batch_size=None):
         self._g = g
         self._nodes = nodes
+        self._size = batch_size
         self._data = data
         self._msgs = msgs
 
@@ -86,10 +92,14 @@ class NodeBatch(object):
         return self._msgs
 
     def nodes(self):
+        if callable(self._nodes):
+            self._nodes = self._nodes()
         return self._nodes
 
     def batch_size(self):
-        return len(self._nodes)
+        if self._size is not None:
+            return self._size
+        return len(self.nodes())
 
     def __len__(self):
         return self.batch_size()

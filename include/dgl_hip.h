@@ -105,6 +105,53 @@ int dglhip_degree_bucketing_host(int64_t num_msgs, const int64_t* msg_recv,
                                  int64_t* nodes, int64_t* msg_ids);
 
 /* ------------------------------------------------------------------------ */
+/* Degree buckets on the device (csrc/degree_buckets.hip): the schedule of   */
+/* dglhip_degree_bucketing_host, built from a receiver-major CSR that is     */
+/* already on the device: indptr int64[num_rows + 1] and slot_msg            */
+/* int64[nnz], the message held by slot k (NULL: slot k holds message k),    */
+/* with a row's slots in message order. dglhip_coo_to_csr_device(row =       */
+/* msg_recv, DGLHIP_ORDER_EID) gives exactly that, with slot_msg = eid.      */
+/* bucket_deg, bucket_node_ptr, nodes and msg_ids are then the host          */
+/* function's arrays for that msg_recv, element for element, cut to their    */
+/* true sizes: bucket_deg[nb], bucket_node_ptr[nb + 1], nodes[listed],       */
+/* msg_ids[nnz] (bucket by bucket, node by node, a node's messages in slot   */
+/* order). Two more arrays describe what the host function leaves to its     */
+/* caller: zero_nodes[num_rows - listed], the rows without messages,         */
+/* ascending, and merge_inv[num_rows], the position of every row in the      */
+/* concatenation nodes ++ zero_nodes (merge_inv[nodes[i]] = i,               */
+/* merge_inv[zero_nodes[j]] = listed + j). All arrays are int64 and the same */
+/* on every run: positions come from a stable sort and scans, the only       */
+/* atomic is an integer counter.                                             */
+/* Two calls share one workspace, with one host read of `status` between     */
+/* them (so neither can run under stream capture):                           */
+/*   status[0] buckets nb, status[1] listed rows (degree > 0), status[2] the */
+/*   largest degree, status[3] items (row chunks of at most                  */
+/*   DGLHIP_BUCKET_CHUNK slots) the fill copies.                             */
+/* indptr values are clamped into [0, nnz]: an indptr that is no CSR's gives */
+/* a wrong schedule, never an access outside the arrays. Receivers are not   */
+/* range-checked here (the CSR build does that). num_rows must be below 2^31.*/
+/* ------------------------------------------------------------------------ */
+#define DGLHIP_BUCKET_CHUNK 512
+/* Bytes of the workspace the two calls share (-1 on an error). */
+int64_t dglhip_degree_buckets_workspace_bytes(int64_t num_rows, int64_t nnz);
+/* Stage A: degrees, the rows sorted by (degree, row id), bucket heads, the
+ * three scans and the item list; fills status (int64[4], device memory). No
+ * host sync inside. */
+int dglhip_degree_buckets_count_device(int64_t num_rows, int64_t nnz, const int64_t* indptr,
+                                       void* workspace, int64_t workspace_bytes,
+                                       int64_t* status, void* stream);
+/* Stage B: writes the six arrays from the workspace stage A left, with
+ * num_buckets = status[0], listed = status[1], items = status[3]. Same sizes
+ * and indptr as stage A. */
+int dglhip_degree_buckets_fill_device(int64_t num_rows, int64_t nnz, const int64_t* indptr,
+                                      const int64_t* slot_msg, void* workspace,
+                                      int64_t workspace_bytes, int64_t num_buckets,
+                                      int64_t listed, int64_t items, int64_t* bucket_deg,
+                                      int64_t* bucket_node_ptr, int64_t* nodes,
+                                      int64_t* zero_nodes, int64_t* msg_ids, int64_t* merge_inv,
+                                      void* stream);
+
+/* ------------------------------------------------------------------------ */
 /* g-SpMM: out[r,:] = REDUCE_{slot k of row r} MSG(ufeat[indices[k],:],      */
 /*                                                  efeat[eid[k],:])        */
 /* Replaces F.spmm / SPMV / SPMV_WITH_DATA (executor.py:452-473,535-566,    */
