@@ -4,7 +4,9 @@ reduce): a count stage, one host read of four status words, a fill stage
 (csrc/induced_subgraph.hip, line_graph.hip, traversal.hip, neighbor_sample.hip,
 degree_buckets.hip, over csrc/compact.h). What their host
 sides share is here once: :class:`_Status`, :func:`_workspace`, :func:`_ids`
-and :func:`_refuse_capture`. ``dgl.kernel`` re-exports the public names.
+and :func:`_refuse_capture`. ``dgl/kernel/__init__.py`` re-exports the public
+names; ``kernel/csr.py`` and ``kernel/rgcn.py`` size their workspaces with
+:func:`_workspace`.
 """
 from __future__ import absolute_import
 

@@ -406,9 +406,9 @@ def test_source_blocked_small(monkeypatch, H, D, bwd):
     adj = adjt[1]
     vals = _values("square", H, D)
     F = H * D
-    monkeypatch.setattr(kernel, "_GAT_BLOCK_BYTES", (F + H) * 4 * 100)
-    monkeypatch.setattr(kernel, "_GAT_BLOCK_BYTES_NOGRAD", (F + H) * 4 * 100)
-    monkeypatch.setattr(kernel, "_GAT_BWD_BLOCK_BYTES", F * 4 * 100)
+    monkeypatch.setattr(kernel.plan, "_GAT_BLOCK_BYTES", (F + H) * 4 * 100)
+    monkeypatch.setattr(kernel.plan, "_GAT_BLOCK_BYTES_NOGRAD", (F + H) * 4 * 100)
+    monkeypatch.setattr(kernel.plan, "_GAT_BWD_BLOCK_BYTES", F * 4 * 100)
     p = 0.5
     ref = _reference(adjt, vals, EXP_CLAMP, True, p)
     old = kernel.set_gat_backward(bwd)

@@ -124,7 +124,7 @@ def test_sage_dense_add_into_equals_sum(monkeypatch):
 
     calls = []
     real = kernel._mean_scaled
-    monkeypatch.setattr(kernel, "_mean_scaled",
+    monkeypatch.setattr(kernel.spmm, "_mean_scaled",
                         lambda *a, **k: calls.append(1) or real(*a, **k))
     res = []
     for agg in (aggregate, fused):

@@ -36,7 +36,7 @@ def main():
         if mib == 0:
             old = kernel.set_blocked("off")
         else:
-            kernel._EL_GRAD_BLOCK_BYTES = mib << 20
+            kernel.plan._EL_GRAD_BLOCK_BYTES = mib << 20
         out = kernel._gat_el_grad(adj, g, H)
         same = bool(torch.equal(out, ref))
         torch.cuda.synchronize()

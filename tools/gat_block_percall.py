@@ -1,4 +1,4 @@
-"""The fused GAT layer's source-block size (kernel._GAT_BLOCK_BYTES) re-swept
+"""The fused GAT layer's source-block size (kernel.plan._GAT_BLOCK_BYTES) re-swept
 by wall time between two events per call (no marker between the launches), on
 the Reddit-shaped graph at 8 heads x 16: forward without and with the
 attention stored, forward + backward; bits compared with the 11 MiB default.
@@ -57,11 +57,11 @@ def main():
         fs, z = kernel.gat_aggregate(adj, ft, el, er)
         torch.autograd.backward([fs, z], [gout, gz])
 
-    kernel._GAT_BLOCK_BYTES = kernel._GAT_BLOCK_BYTES_NOGRAD = 11 << 20
+    kernel.plan._GAT_BLOCK_BYTES = kernel.plan._GAT_BLOCK_BYTES_NOGRAD = 11 << 20
     ref = [t.detach().clone() for t in fwd_ng()]
     res = {"graph": "reddit_like", "rows": []}
     for mib in args.mib:
-        kernel._GAT_BLOCK_BYTES = kernel._GAT_BLOCK_BYTES_NOGRAD = int(mib * (1 << 20))
+        kernel.plan._GAT_BLOCK_BYTES = kernel.plan._GAT_BLOCK_BYTES_NOGRAD = int(mib * (1 << 20))
         same = all(torch.equal(a, b) for a, b in zip(fwd_ng(), ref))
         row = {"block_MiB": mib, "fwd_ms": wall(fwd_ng, args.iters),
                "fwd_stored_ms": wall(fwd_g, args.iters), "fwd_bwd_ms": wall(fb, args.iters),

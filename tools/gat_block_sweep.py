@@ -40,7 +40,7 @@ def main():
         for s in sizes:
             pol = kernel.set_blocked("off" if s == 0 else "auto")
             if s:
-                kernel._GAT_BLOCK_BYTES = s
+                kernel.plan._GAT_BLOCK_BYTES = s
             with torch.no_grad():
                 out = kernel.gat_aggregate(adj, ft, el, er)
                 assert torch.equal(out[0], ref[0]) and torch.equal(out[1], ref[1]), s

@@ -1,5 +1,5 @@
 """Source-block size of the one-pass GAT backward over the transpose
-(kernel._GAT_BWD_BLOCK_BYTES), Reddit-shaped graph, 8 heads x 16: forward +
+(kernel.plan._GAT_BWD_BLOCK_BYTES), Reddit-shaped graph, 8 heads x 16: forward +
 backward wall ms per size, interleaved over rounds, gradients vs the default.
 
   python tools/gat_bwd_sweep.py [--rounds 3] [--out file.json]
@@ -52,20 +52,20 @@ def main():
         e.record()
         e.synchronize()
         return s.elapsed_time(e) / args.iters
-    default = kernel._GAT_BWD_BLOCK_BYTES
+    default = kernel.plan._GAT_BWD_BLOCK_BYTES
     ref = fb()
     res, same, launches = {}, {}, {}
     try:
         for _ in range(args.rounds):
             for mib in args.mib:
-                kernel._GAT_BWD_BLOCK_BYTES = mib << 20
+                kernel.plan._GAT_BWD_BLOCK_BYTES = mib << 20
                 got = fb()
                 same[mib] = all(bool(torch.equal(a, b)) for a, b in zip(got, ref))
                 plan = kernel._block_plan(adj.bwd, gout.view(n, 128), 128, mib << 20)
                 launches[mib] = 0 if plan is None else len(plan)
                 res.setdefault(mib, []).append(wall())
     finally:
-        kernel._GAT_BWD_BLOCK_BYTES = default
+        kernel.plan._GAT_BWD_BLOCK_BYTES = default
     line = json.dumps({"fwd_bwd_ms": res, "min": {k: min(v) for k, v in res.items()},
                        "launches": launches, "bit_identical": same})
     print(line)
