@@ -17,7 +17,7 @@ from .base import ALL, DGLError  # noqa: F401
 from .graph import DGLGraph  # noqa: F401
 from .batched_graph import (BatchedDGLGraph, batch, unbatch, split,  # noqa: F401
                             sum_nodes, sum_edges, mean_nodes, mean_edges,
-                            max_nodes, max_edges)
+                            max_nodes, max_edges, softmax_nodes, softmax_edges)
 from .subgraph import DGLSubGraph  # noqa: F401
 from .traversal import *  # noqa: F401,F403
 from .propagate import *  # noqa: F401,F403

@@ -225,6 +225,13 @@ def _load():
                                              [_c_i64] + [_vp] * 7),
         "dglhip_segment_reduce_bwd_host": (_c_int, [_c_int, _c_i64, _c_i64, _c_i64] + [_vp] * 3 +
                                            [_c_i64] + [_vp] * 6 + [_c_int]),
+        "dglhip_edge_softmax_workspace_bytes": (_c_i64, [_c_i64, _c_i64, _c_i64]),
+        "dglhip_edge_softmax_device": (_c_int, [_c_i64, _c_i64, _c_i64] + [_vp] * 5 +
+                                       [_c_i64, _vp, _vp]),
+        "dglhip_edge_softmax_bwd_device": (_c_int, [_c_i64, _c_i64, _c_i64] + [_vp] * 6 +
+                                           [_c_i64, _vp, _vp]),
+        "dglhip_edge_softmax_host": (_c_int, [_c_i64, _c_i64, _c_i64] + [_vp] * 4 + [_c_int]),
+        "dglhip_edge_softmax_bwd_host": (_c_int, [_c_i64, _c_i64, _c_i64] + [_vp] * 5 + [_c_int]),
         "dglhip_induced_subgraph_workspace_bytes": (_c_i64, [_c_i64, _c_i64, _c_i64]),
         "dglhip_induced_subgraph_count_device": (_c_int, [_c_i64, _c_i64, _c_i64, _vp, _vp, _vp,
                                                           _vp, _c_i64, _vp, _vp]),

@@ -10,6 +10,8 @@ Where the reference delegates readout to ``scatter_add_`` and a Python loop of
 ``torch.max`` per graph (batched_graph.py:362-399,542-588,730-766), every
 readout here is one call of ``kernel.segment_reduce``: a batch's nodes (and
 edges) of one graph are consecutive rows, so the graphs are the segments.
+``softmax_nodes`` / ``softmax_edges`` normalise a feature over each member
+graph the same way, on the edge-softmax kernel (``kernel.segment_softmax``).
 """
 from __future__ import absolute_import
 
@@ -24,7 +26,7 @@ from .frame import Frame
 from .graph import DGLGraph
 
 __all__ = ["BatchedDGLGraph", "batch", "unbatch", "split", "sum_nodes", "sum_edges",
-           "mean_nodes", "mean_edges", "max_nodes", "max_edges"]
+           "mean_nodes", "mean_edges", "max_nodes", "max_edges", "softmax_nodes", "softmax_edges"]
 
 
 def _items_and_fields(g, mode):
@@ -222,3 +224,24 @@ def max_nodes(graph, feat):
 def max_edges(graph, feat):
     """:func:`max_nodes` over edge fields."""
     return _readout(graph, "edges", feat, None, "max")
+
+
+def _softmax_readout(graph, typestr, feat):
+    x = (graph.ndata if typestr == "nodes" else graph.edata)[feat]
+    if isinstance(graph, BatchedDGLGraph):
+        return kernel.segment_softmax(x, graph._readout_segments(typestr))
+    # a plain graph is one segment
+    return kernel.segment_softmax(x, kernel.SegmentOffsets(sizes=[x.shape[0]]))
+
+
+def softmax_nodes(graph, feat):
+    """Node field ``feat`` normalised by a softmax over the nodes of each
+    graph of the batch (of the whole graph for a plain one), every feature
+    position on its own: a tensor of the field's shape, differentiable in it.
+    A graph without nodes contributes nothing."""
+    return _softmax_readout(graph, "nodes", feat)
+
+
+def softmax_edges(graph, feat):
+    """:func:`softmax_nodes` over edge fields."""
+    return _softmax_readout(graph, "edges", feat)

@@ -28,7 +28,7 @@ spmm -> {rgcn, gat, segment}: ``policy`` (constants, the schedule policy),
 ``plan`` (the views of the native launch plan), ``csr`` (CSR, SparseAdj and
 their builders), ``spmm`` (g-SpMM / g-SDDMM, call timing), ``rgcn``
 (gather_rows, DistMult, the typed-block operator), ``gat`` (edge attention,
-the fused GAT layer), ``segment`` (the segment reduction). This file only
+the fused GAT layer, the edge softmax), ``segment`` (the segment reduction). This file only
 re-exports them, so callers keep ``kernel.<name>``.
 
 A setting that is rebound after import lives in one module, which reads it at
@@ -74,7 +74,8 @@ from .rgcn import (  # noqa: F401
     _typed_scale_fused, typed_block_spmm)
 from .gat import (  # noqa: F401
     edge_attention, set_gat_backward, set_gat_variant, gat_dropout_scale, gat_dropout_mask,
-    _GATAggregate, _gat_el_grad, gat_aggregate, gat_logits, _logits_source)
+    _GATAggregate, _gat_el_grad, gat_aggregate, gat_logits, _logits_source,
+    EDGE_SOFTMAX_CHUNK, edge_softmax, segment_softmax)
 from .segment import SEGMENT_CHUNK, SegmentOffsets, segment_reduce  # noqa: F401
 
 __all__ = ["CSR", "SparseAdj", "build_csr", "gspmm", "gsddmm_dot",

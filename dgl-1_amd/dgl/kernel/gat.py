@@ -1,5 +1,7 @@
-"""GAT's operators: the per-edge attention, the fused aggregation layer with
-its backwards, and the attention logits (csrc/gat_fused.hip)."""
+"""The edge-attention operators: GAT's per-edge attention, its fused
+aggregation layer with its backwards and its attention logits
+(csrc/gat_fused.hip), and the softmax over a node's edges
+(csrc/edge_softmax.hip)."""
 from __future__ import absolute_import
 
 import os
@@ -10,6 +12,7 @@ import torch
 
 from .._ffi import LIB, check_call, ptr, stream_of as _stream_of
 from ..base import DGLError
+from ..device_graph import _workspace
 # the block sizes are read as _plan.<name> at call time: plan owns them
 from . import plan as _plan
 from .policy import MSG_U_MUL_E, MSG_COPY_E, RED_SUM, SLOT, schedule_policy
@@ -524,3 +527,111 @@ def _logits_source(el, ft):
             ft._version != version or el._version != el_version):
         return None
     return al if al.device == ft.device else None
+
+
+# ---------------------------------------------------------------------------
+# Edge softmax: the softmax of per-edge scores over each row's slots
+# (csrc/edge_softmax.hip)
+# ---------------------------------------------------------------------------
+EDGE_SOFTMAX_CHUNK = 1024  # DGLHIP_EDGE_SOFTMAX_CHUNK: a longer row is cut into pieces
+
+
+def _softmax_run(rows, x, dy):
+    """The forward over the scores ``x`` (``dy`` None) or the backward from
+    the forward's ``x`` = y and ``dy``, both (nnz, H) float32 contiguous.
+    ``rows``: (num_rows, indptr, eid or None, row_order or None, the longest
+    row or -1)."""
+    R, indptr, eid, row_order, max_len = rows
+    nnz, H = x.shape
+    dev = x.device
+    out = torch.empty_like(x)
+    if dev.type == "cuda":
+        nbytes = 0
+        if max_len < 0 or max_len > EDGE_SOFTMAX_CHUNK:
+            nbytes = LIB.dglhip_edge_softmax_workspace_bytes(R, nnz, H)
+        ws = _workspace(nbytes, dev) if nbytes else None
+        head = (R, nnz, H, ptr(indptr), ptr(eid), ptr(row_order))
+        tail = (ptr(out), max_len, ptr(ws), _stream_of(dev))
+        if dy is None:
+            check_call(LIB.dglhip_edge_softmax_device(*(head + (ptr(x),) + tail)))
+        else:
+            check_call(LIB.dglhip_edge_softmax_bwd_device(*(head + (ptr(x), ptr(dy)) + tail)))
+    elif dy is None:
+        check_call(LIB.dglhip_edge_softmax_host(R, nnz, H, ptr(indptr), ptr(eid), ptr(x),
+                                                ptr(out), 0))
+    else:
+        check_call(LIB.dglhip_edge_softmax_bwd_host(R, nnz, H, ptr(indptr), ptr(eid), ptr(x),
+                                                    ptr(dy), ptr(out), 0))
+    return out
+
+
+class _EdgeSoftmax(torch.autograd.Function):
+    """y = softmax of x over the slots of each row; dx = y * (dy - sum y dy)."""
+
+    @staticmethod
+    def forward(ctx, x, rows):
+        y = _softmax_run(rows, x, None)
+        ctx.rows = rows
+        ctx.save_for_backward(y)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        (y,) = ctx.saved_tensors
+        return _softmax_run(ctx.rows, y, _f32c(dy)), None
+
+
+def _softmax_columns(x, what):
+    """``x`` (rows, ...) as (rows, H) float32 contiguous."""
+    if not isinstance(x, torch.Tensor) or x.dim() < 1:
+        raise DGLError("%s expects a tensor of rows" % what)
+    H = 1
+    for d in x.shape[1:]:
+        H *= d
+    return _f32c(x.reshape(x.shape[0], H))
+
+
+def edge_softmax(adj, logits, norm_by="dst", edge_order="eid"):
+    """The softmax of the edge scores ``logits`` over the in-edges of every
+    destination (``norm_by="dst"``, the rows of ``adj.fwd``) or the out-edges
+    of every source (``"src"``, the rows of ``adj.bwd``), one kernel forward
+    and one backward (csrc/edge_softmax.hip). ``logits`` is ``(E,)`` or
+    ``(E, ...)`` float32 indexed by edge id, every trailing position its own
+    softmax; the result has its shape. ``edge_order="slot"``
+    (``norm_by="dst"`` only) takes and returns values in forward-CSR slot
+    order, as ``gspmm`` and ``edge_attention`` do.
+
+    Per group: y = expf(x - max x) / sum, in float32; a NaN or +inf makes the
+    group NaN, -inf beside a finite maximum gives 0, a node without edges
+    contributes nothing. The same bits on every call (no atomics); the sum's
+    order is the kernel's, not the slot order."""
+    if norm_by not in ("dst", "src"):
+        raise DGLError("norm_by must be 'dst' or 'src', got %r" % (norm_by,))
+    slot = edge_order_of(adj, edge_order)
+    if slot and norm_by != "dst":
+        raise DGLError("edge_order='slot' is the forward CSR's order: norm_by='dst' only")
+    x = _softmax_columns(logits, "edge_softmax")
+    adj = adj.to(logits.device)
+    csr = adj.fwd if norm_by == "dst" else adj.bwd
+    if x.shape[0] != csr.nnz:
+        raise DGLError("edge_softmax: %d rows of logits for %d edges" % (x.shape[0], csr.nnz))
+    if x.numel() == 0:
+        return torch.empty_like(logits)
+    rows = (csr.num_rows, csr.indptr, None if slot else csr.slot_eid, csr.row_order,
+            csr.max_degree)
+    return _EdgeSoftmax.apply(x, rows).view(logits.shape)
+
+
+def segment_softmax(x, segments):
+    """The softmax of ``x`` (N, ...) float32 over each consecutive row range
+    of ``segments`` (a :class:`SegmentOffsets`), every trailing position its
+    own softmax: the edge-softmax kernel with the offsets as its row pointer
+    and no edge ids. Differentiable; the result has ``x``'s shape."""
+    x2 = _softmax_columns(x, "segment_softmax")
+    N = x2.shape[0]
+    if segments.num_rows >= 0 and segments.num_rows != N:
+        raise DGLError("offsets end at %d, expected the %d rows" % (segments.num_rows, N))
+    if x2.numel() == 0 or segments.num_segments == 0:
+        return torch.empty_like(x)
+    rows = (segments.num_segments, segments.on(x.device), None, None, segments.max_rows)
+    return _EdgeSoftmax.apply(x2, rows).view(x.shape)

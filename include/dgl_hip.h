@@ -533,6 +533,60 @@ int dglhip_segment_reduce_bwd_host(int reduce_op, int64_t num_segments, int64_t 
                                    float* dx, float* dw, int num_threads);
 
 /* ------------------------------------------------------------------------ */
+/* Edge softmax (csrc/edge_softmax.hip): the softmax of per-edge scores over */
+/* the edges of each node, and over the nodes or edges of each graph of a    */
+/* batch. The rows of a CSR are the groups: indptr int64[num_rows + 1],      */
+/* non-decreasing from 0 to nnz; the slots of row r are k in [indptr[r],     */
+/* indptr[r+1]). x: float32 [num_edges, feat_len] packed; slot k holds       */
+/* x[eid[k], :] (eid int64[nnz]), or x[k, :] when eid is NULL.               */
+/* Forward, per row r and column h, in float32:                              */
+/*   m = max_k x[k, h], e_k = expf(x[k, h] - m), s = sum_k e_k,              */
+/*   y[k, h] = e_k / s, stored where x[k, h] was read from.                  */
+/* Per (row, column) group the special values are torch.softmax's: a NaN or  */
+/* a +inf makes the group NaN, -inf beside a finite maximum gives exactly 0, */
+/* a group of only -inf is NaN, one finite value gives exactly 1.0. A row    */
+/* without slots writes nothing.                                             */
+/* Backward, from dy and the forward's y, both in x's layout:                */
+/*   t = sum_k y[k, h] * dy[k, h], dx[k, h] = y[k, h] * (dy[k, h] - t).      */
+/* The sums are combined across lanes and waves in a fixed order that is not */
+/* the slot order: the same bits on every call, no atomics, every element of */
+/* y / dx written exactly once. Host and device differ in the last bits      */
+/* (their expf differ).                                                      */
+/* A row of at most DGLHIP_EDGE_SOFTMAX_CHUNK slots is taken by one wave (a  */
+/* part of one when it is short). A longer row is cut where it crosses the   */
+/* multiples of that many slots; each piece is a workgroup's, its (max, sum) */
+/* goes to `workspace`, and a row's pieces are combined in slot order.       */
+/* ------------------------------------------------------------------------ */
+#define DGLHIP_EDGE_SOFTMAX_CHUNK 1024
+/* Bytes of the device forms' workspace (0: none needed); the forward and the
+ * backward take the same. */
+int64_t dglhip_edge_softmax_workspace_bytes(int64_t num_rows, int64_t nnz, int64_t feat_len);
+/* Device forms: all pointers are device pointers. row_order (int32[num_rows]
+ * or NULL) only schedules the launch (rows by degree, descending).
+ * max_row_len: the longest row if the caller knows it (<=
+ * DGLHIP_EDGE_SOFTMAX_CHUNK skips the work on long rows and needs no
+ * workspace), -1 if not. Launch sizes come from num_rows, nnz, feat_len and
+ * max_row_len alone: no host sync, no allocation. indptr entries are clamped
+ * to [0, nnz], never followed beyond. */
+int dglhip_edge_softmax_device(int64_t num_rows, int64_t nnz, int64_t feat_len,
+                               const int64_t* indptr, const int64_t* eid,
+                               const int32_t* row_order, const float* x, float* y,
+                               int64_t max_row_len, void* workspace, void* stream);
+int dglhip_edge_softmax_bwd_device(int64_t num_rows, int64_t nnz, int64_t feat_len,
+                                   const int64_t* indptr, const int64_t* eid,
+                                   const int32_t* row_order, const float* y, const float* dy,
+                                   float* dx, int64_t max_row_len, void* workspace,
+                                   void* stream);
+/* Host forms (thread pool), one sequential pass per row. An indptr that does
+ * not start at 0, decreases or does not end at nnz returns -1 with a message. */
+int dglhip_edge_softmax_host(int64_t num_rows, int64_t nnz, int64_t feat_len,
+                             const int64_t* indptr, const int64_t* eid, const float* x,
+                             float* y, int num_threads);
+int dglhip_edge_softmax_bwd_host(int64_t num_rows, int64_t nnz, int64_t feat_len,
+                                 const int64_t* indptr, const int64_t* eid, const float* y,
+                                 const float* dy, float* dx, int num_threads);
+
+/* ------------------------------------------------------------------------ */
 /* Node-induced subgraph on the device (csrc/induced_subgraph.hip): the      */
 /* reference's Graph::VertexSubgraph (src/graph/graph.cc:441-469) over a     */
 /* source-major CSR that is already on the device: indptr int64[num_nodes +  */
