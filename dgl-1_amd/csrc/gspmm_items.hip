@@ -172,16 +172,30 @@ __device__ __forceinline__ uint32_t row_broadcast(uint32_t v, int j) {
 // order, so there is no workgroup barrier. A wave above the cap (the long
 // items at the head of a launch) loads its ids batch by batch.
 constexpr int kItemsColumnsIdsCap = 1024;
+// IDS16 (DESIGN.md §4.1 "Column halves", slice-local ids): the launch's slots
+// hold 16-bit ids local to its source block, `ids` is the plan's uint16 array
+// and `ufeat` / `table_bytes` are the block's first row and its bytes (the
+// launcher's: the block is shorter than 4 GiB - 1 KiB, the table may be
+// longer), so the offsets are block-relative. Lane l still reads slot l of
+// its load, a ushort in place of a dword: the same lanes, slots and adds.
+// kIds16Aux: the cache policy of those loads (0 default, 2 non-temporal as
+// load_row's; both measured, profiles/r32/ids16).
+#ifndef DGLHIP_IDS16_AUX
+#define DGLHIP_IDS16_AUX 0
+#endif
+constexpr int kIds16Aux = DGLHIP_IDS16_AUX;
 
-template <int DEPTH, bool ACCUM>
+template <int DEPTH, bool ACCUM, bool IDS16>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void
 gspmm_items_columns_kernel(
     int64_t num_items, int64_t ldu, uint32_t table_bytes, uint32_t out_bytes,
-    const int32_t* __restrict__ indices, const float* __restrict__ ufeat,
+    const void* __restrict__ ids, const float* __restrict__ ufeat,
     float* __restrict__ out, const int32_t* __restrict__ item_rows,
     const int64_t* __restrict__ item_ptr) {
   static_assert(DEPTH >= 1 && DEPTH <= 16, "a batch's ids are one 16-lane row");
   typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+  typedef std::conditional_t<IDS16, uint16_t, int32_t> id_t;
+  const id_t* __restrict__ indices = static_cast<const id_t*>(ids);
   constexpr uint32_t kOff = 0xfffffc00u;  // + any lane offset: past every gated table
   const int lane = threadIdx.x & 63;
   const int q = lane >> 4, ql = lane & 15;
@@ -235,8 +249,16 @@ gspmm_items_columns_kernel(
   // load past the wave's last slot is answered without a fetch
   const int64_t total = p[4] - p[0];
   const __amdgpu_buffer_rsrc_t slots = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<int32_t*>(indices + p[0]), 0,
-      static_cast<int>(min(total * 4, int64_t(0x7fffffff))), 0x00020000);
+      const_cast<id_t*>(indices + p[0]), 0,
+      static_cast<int>(min(total * int64_t(sizeof(id_t)), int64_t(0x7fffffff))), 0x00020000);
+  // the id of the wave's slot s (IDS16: zero-extended)
+  auto load_slot = [&](uint32_t s) -> uint32_t {
+    if constexpr (IDS16)
+      return static_cast<uint16_t>(
+          __builtin_amdgcn_raw_buffer_load_b16(slots, s * 2u, 0, kIds16Aux));
+    else
+      return __builtin_amdgcn_raw_buffer_load_b32(slots, s * 4u, 0, 0);
+  };
   // all of out behind one (the gate: shorter than 4 GiB): lane ln's 16 bytes
   // of its quarter's row
   const __amdgpu_buffer_rsrc_t rows = __builtin_amdgcn_make_buffer_rsrc(
@@ -273,7 +295,7 @@ gspmm_items_columns_kernel(
       const int s = max(min(k + ql, my_n - 1) + my_rel, 0);
       if constexpr (PRELOADED) return wids[s];
       else
-        return __builtin_amdgcn_raw_buffer_load_b32(slots, static_cast<uint32_t>(s) * 4u, 0, 0);
+        return load_slot(static_cast<uint32_t>(s));
     };
     auto offsets = [&](uint32_t id, int k) -> uint32_t {
       return k + ql < my_n ? (PRELOADED ? id : id * ld4) : kOff;
@@ -295,8 +317,7 @@ gspmm_items_columns_kernel(
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
           if (u == 0 || c + 64 * u < T)
-            g[u] = __builtin_amdgcn_raw_buffer_load_b32(
-                slots, static_cast<uint32_t>(c + 64 * u + lane) * 4u, 0, 0);
+            g[u] = load_slot(static_cast<uint32_t>(c + 64 * u + lane));
         }
       };
       auto write_group = [&](int c) {
@@ -422,6 +443,11 @@ struct ItemsLaunch {
   const int64_t* item_ptr;
   const int32_t* indices;
   bool accumulate;
+  // 16-bit ids local to the launch's source block (nullptr: indices): rows
+  // [col_lo, col_lo + block_rows) of ufeat, slot s gathering row col_lo + ids16[s]
+  const uint16_t* ids16 = nullptr;
+  int64_t col_lo = 0;
+  int64_t block_rows = 0;
 };
 
 // Whether a copy_u launch of the blocked schedule's items takes the two-
@@ -445,6 +471,21 @@ static inline bool items_columns_applies(const ItemsLaunch& a) {
   const int64_t ldu = a.ldu ? a.ldu : a.F;
   return a.column_parts == 2 && items_pair_applies(a) &&
          a.urows * ldu * int64_t(sizeof(float)) <= int64_t(0xfffffc00u) && a.orows > 0 &&
+         a.orows * a.F * int64_t(sizeof(float)) < (int64_t(1) << 32);
+}
+
+// Whether a launch with 16-bit block-local ids takes the column-half kernel:
+// its gate with the block's bytes in place of the whole table's (the
+// descriptor covers the block alone, so a table past 4 GiB qualifies block by
+// block), ids that fit 16 bits, and the block inside the table.
+static inline bool items_columns_ids16_applies(const ItemsLaunch& a) {
+  const int64_t ldu = a.ldu ? a.ldu : a.F;
+  return a.ids16 != nullptr && a.msg == DGLHIP_MSG_COPY_U && a.items_per_wave == 2 &&
+         a.column_parts == 2 && a.F == 128 && ldu % 4 == 0 &&
+         reinterpret_cast<uintptr_t>(a.ufeat) % 16 == 0 &&
+         reinterpret_cast<uintptr_t>(a.out) % 16 == 0 && a.col_lo >= 0 && a.block_rows > 0 &&
+         a.block_rows <= 65536 && a.col_lo + a.block_rows <= a.urows &&
+         a.block_rows * ldu * int64_t(sizeof(float)) <= int64_t(0xfffffc00u) && a.orows > 0 &&
          a.orows * a.F * int64_t(sizeof(float)) < (int64_t(1) << 32);
 }
 
@@ -472,13 +513,20 @@ static inline void launch_items_columns(const ItemsLaunch& a, hipStream_t stream
   const int64_t blocks = 2 * ((a.num_items + 15) / 16);
   DGLHIP_CHECK(blocks <= 0x7fffffff, "grid too large: " << blocks);
   const int64_t ldu = a.ldu ? a.ldu : a.F;
-  auto kernel = a.accumulate ? gspmm_items_columns_kernel<DEPTH, true>
-                             : gspmm_items_columns_kernel<DEPTH, false>;
+  // 16-bit ids: the table the kernel sees is the launch's source block
+  const bool ids16 = a.ids16 != nullptr;
+  auto kernel = ids16 ? (a.accumulate ? gspmm_items_columns_kernel<DEPTH, true, true>
+                                      : gspmm_items_columns_kernel<DEPTH, false, true>)
+                      : (a.accumulate ? gspmm_items_columns_kernel<DEPTH, true, false>
+                                      : gspmm_items_columns_kernel<DEPTH, false, false>);
+  const int64_t rows = ids16 ? a.block_rows : a.urows;
+  const float* table = ids16 ? a.ufeat + a.col_lo * ldu : a.ufeat;
+  const void* ids = ids16 ? static_cast<const void*>(a.ids16) : a.indices;
   timed_launch(stream, [&] {
     hipLaunchKernelGGL(kernel, grid_1d(blocks), dim3(256), 0, stream, a.num_items, ldu,
-                       static_cast<uint32_t>(a.urows * ldu * int64_t(sizeof(float))),
-                       static_cast<uint32_t>(a.orows * a.F * int64_t(sizeof(float))), a.indices,
-                       a.ufeat, a.out, a.item_rows, a.item_ptr);
+                       static_cast<uint32_t>(rows * ldu * int64_t(sizeof(float))),
+                       static_cast<uint32_t>(a.orows * a.F * int64_t(sizeof(float))), ids, table,
+                       a.out, a.item_rows, a.item_ptr);
   });
 }
 
@@ -527,6 +575,25 @@ void gspmm_items_columns(int msg_op, int64_t num_items, int64_t feat_len, const 
   }
 }
 
+bool gspmm_items_columns_ids16(int64_t num_items, const int32_t* item_rows,
+                               const int64_t* item_ptr, int accumulate, const uint16_t* ids16,
+                               int64_t col_lo, int64_t block_rows, const float* ufeat,
+                               int64_t ufeat_ld, int64_t ufeat_rows, float* out, int64_t out_rows,
+                               hipStream_t stream) {
+  DGLHIP_CHECK(num_items >= 0 && ufeat_rows >= 0 && out_rows >= 0, "negative size");
+  if (num_items == 0) return true;
+  DGLHIP_CHECK(item_rows && item_ptr && ids16 && ufeat && out, "null items/ids/ufeat/out");
+  check_ufeat_ld(ufeat_ld, 128);
+  ItemsLaunch a{DGLHIP_MSG_COPY_U, 128, ufeat_ld, ufeat_rows, out_rows, 2, 2, ufeat, out,
+                num_items, item_rows, item_ptr, nullptr, accumulate != 0};
+  a.ids16 = ids16;
+  a.col_lo = col_lo;
+  a.block_rows = block_rows;
+  if (!items_columns_ids16_applies(a)) return false;
+  launch_items_columns(a, stream);
+  return true;
+}
+
 }  // namespace dglhip
 
 using namespace dglhip;
@@ -558,6 +625,22 @@ int dglhip_gspmm_items_columns_device(int msg_op, int64_t num_items, int64_t fea
   gspmm_items_columns(msg_op, num_items, feat_len, item_rows, item_ptr, accumulate, indices, eid,
                       ufeat, ufeat_ld, ufeat_rows, items_per_wave, column_parts, efeat, efeat_len,
                       out, 0, static_cast<hipStream_t>(stream_));
+  API_END();
+}
+
+int dglhip_gspmm_items_ids16_device(int64_t num_items, const int32_t* item_rows,
+                                    const int64_t* item_ptr, int accumulate,
+                                    const uint16_t* ids16, int64_t col_lo, int64_t block_rows,
+                                    const float* ufeat, int64_t ufeat_ld, int64_t ufeat_rows,
+                                    float* out, int64_t out_rows, void* stream_) {
+  API_BEGIN();
+  // this entry is the 16-bit kernel or nothing: no other kernel reads these ids
+  DGLHIP_CHECK(gspmm_items_columns_ids16(num_items, item_rows, item_ptr, accumulate, ids16, col_lo,
+                                         block_rows, ufeat, ufeat_ld, ufeat_rows, out, out_rows,
+                                         static_cast<hipStream_t>(stream_)),
+               "16-bit ids: rows [" << col_lo << ", " << col_lo + block_rows << ") of "
+                                    << ufeat_rows << " into " << out_rows
+                                    << " rows do not take the column-half kernel");
   API_END();
 }
 

@@ -285,12 +285,19 @@ void register_kernel_functions() {
       meta.push_back(it.off);
       meta.push_back(it.suffix ? 1 : 0);
     }
+    // behind the launches: the split (first column, columns per block, span)
+    // and whether the 16-bit block-local ids exist (the last array then)
+    meta.push_back(bp->lo);
+    meta.push_back(bp->bs);
+    meta.push_back(bp->span);
+    meta.push_back(bp->has_ids16 ? 1 : 0);
     std::vector<rt::NDArray> vec = {rt::NDArray::FromVector(meta), bp->indices, bp->pos,
                                     bp->absent};
     for (const BlockItems& it : bp->launches) {
       vec.push_back(it.rows);
       vec.push_back(it.ptr);
     }
+    if (bp->has_ids16) vec.push_back(bp->ids16);
     rv->set_func(rt::ndarray_vector_func(std::move(vec)));
   });
   // (plan, row_bytes, block_bytes, blocks (0: from the sizes), stream)

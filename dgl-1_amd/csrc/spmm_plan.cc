@@ -56,6 +56,7 @@ SpmmPolicy policy_from_env() {
   p.pad_rows = env_str("DGLHIP_PAD_ROWS", "auto") == "auto";
   p.items_per_wave = env_str("DGLHIP_ITEMS_PER_WAVE", "2") == "1" ? 1 : 2;
   p.column_parts = env_str("DGLHIP_COLUMN_PARTS", "2") == "1" ? 1 : 2;
+  p.ids_wide = env_str("DGLHIP_IDS_WIDE", "0") == "1" ? 1 : 0;
   return p;
 }
 
@@ -133,6 +134,7 @@ void set_spmm_policy(const SpmmPolicy& p) {
                "items_per_wave " << p.items_per_wave << ": 1 or 2");
   DGLHIP_CHECK(p.column_parts == 1 || p.column_parts == 2,
                "column_parts " << p.column_parts << ": 1 or 2");
+  DGLHIP_CHECK(p.ids_wide == 0 || p.ids_wide == 1, "ids_wide " << p.ids_wide << ": 0 or 1");
   std::lock_guard<std::mutex> lk(g_pol_mu);
   pol_ref() = p;
 }
@@ -448,13 +450,23 @@ std::shared_ptr<BlockedPlan> SpmmPlan::blocked_for(int B, hipStream_t s) {
   bp->pos = empty({nnz_}, 0, 32);
   int32_t* oi = bp->indices.data<int32_t>();
   int32_t* op = bp->pos.data<int32_t>();
+  // 16-bit block-local ids beside them, where a block's columns fit
+  bp->lo = split->lo;
+  bp->bs = split->bs;
+  bp->span = hi_ - lo_;
+  bp->has_ids16 = split->bs <= 65536;
+  uint16_t* o16 = nullptr;
+  if (bp->has_ids16) {
+    bp->ids16 = empty({nnz_}, 0, 16);
+    o16 = bp->ids16.data<uint16_t>();
+  }
   if (on_device()) {
     rt::NDArray ist = upload(item_start.data(), R_ * B, 0, 64, s);
     rt::NDArray sst = upload(sfx_start.data(), R_, 0, 64, s);
     rt::NDArray pend = upload(split->pend.data(), R_, 0, 64, s);
     plan_block_scatter_device(R_, indptr_, indices_, split->lo, split->bs, B,
                               pend.data<int64_t>(), ist.data<int64_t>(), sst.data<int64_t>(), oi,
-                              op, s);
+                              op, o16, s);
     hip_ok(hipStreamSynchronize(s), "plan scatter");  // the staging arrays go out of scope
   } else {
     const int64_t lo = split->lo, bs = split->bs;
@@ -469,11 +481,13 @@ std::shared_ptr<BlockedPlan> SpmmPlan::blocked_for(int B, hipStream_t s) {
           const int64_t dst = item_start[r * B + b] + (k - run_s);
           oi[dst] = indices_[k];
           op[dst] = static_cast<int32_t>(k);
+          if (o16) o16[dst] = static_cast<uint16_t>(indices_[k] - (lo + b * bs));
         }
         for (int64_t k = pe; k < ip[r + 1]; ++k) {
           const int64_t dst = sfx_start[r] + (k - pe);
           oi[dst] = indices_[k];
           op[dst] = static_cast<int32_t>(k);
+          if (o16) o16[dst] = static_cast<uint16_t>(indices_[k] - lo);
         }
       }
     });
@@ -615,7 +629,7 @@ std::shared_ptr<SweepPlan> SpmmPlan::sweep(int64_t row_bytes, int mode, hipStrea
     rt::NDArray pend = upload(split->pend.data(), R_, 0, 64, s);
     plan_block_scatter_device(R_, indptr_, indices_, split->lo, split->bs, B,
                               pend.data<int64_t>(), ist.data<int64_t>(), nullptr,
-                              sw->lay.data<int32_t>(), sw->pos.data<int32_t>(), s);
+                              sw->lay.data<int32_t>(), sw->pos.data<int32_t>(), nullptr, s);
     sw->seg = upload(seg.data(), W * B, 0, 64, s);
     sw->counts = upload(cnt, R_ * B, 0, 32, s);
     hip_ok(hipStreamSynchronize(s), "sweep layout");  // the staging arrays go out of scope
@@ -1082,8 +1096,24 @@ void run_planned(SpmmPlan& plan, const RunArgs& a, const Decision& d, void* work
         erows = rows;
       }
     }
+    // 16-bit block-local ids for the column halves' launches (policy word
+    // ids_wide 0): a block launch's columns are [lo + i * bs, + bs), the
+    // suffix's the whole span, which takes them only when it fits 16 bits. A
+    // launch the gate declines runs over the int32 ids below.
+    const bool ids16 = bp.has_ids16 && !p.ids_wide && a.msg == DGLHIP_MSG_COPY_U && a.F == 128 &&
+                       d.items_per_wave == 2 && d.column_parts == 2;
     for (size_t i = 0; i < bp.launches.size(); ++i) {
       const BlockItems& it = bp.launches[i];
+      if (ids16 && (!it.suffix || bp.span <= 65536)) {
+        const int64_t col_lo = it.suffix ? bp.lo : bp.lo + static_cast<int64_t>(i) * bp.bs;
+        const int64_t rows = std::min(it.suffix ? bp.span : bp.bs, a.urows - col_lo);
+        if (gspmm_items_columns_ids16(it.n_items, it.rows.data<int32_t>(), it.ptr.data<int64_t>(),
+                                      (i == 0 && first_writes) ? 0 : 1,
+                                      bp.ids16.data<uint16_t>(), col_lo, rows,
+                                      static_cast<const float*>(uf), d.ld, a.urows, sums,
+                                      plan.num_rows(), s))
+          continue;
+      }
       gspmm_items_columns(a.msg, it.n_items, a.F, it.rows.data<int32_t>(), it.ptr.data<int64_t>(),
                           (i == 0 && first_writes) ? 0 : 1, bp.indices.data<int32_t>(),
                           ev ? nullptr : erows, static_cast<const float*>(uf), d.ld, a.urows,
@@ -1301,7 +1331,7 @@ int dglhip_spmm_get_policy(DGLHipSpmmPolicy* out) {
   out->tier_min_rows = p.tier_min_rows;
   out->pad_min_bytes = p.pad_min_bytes;
   out->column_parts = p.column_parts;
-  out->reserved = 0;
+  out->ids_wide = p.ids_wide;
   API_END();
 }
 
@@ -1324,6 +1354,7 @@ int dglhip_spmm_set_policy(const DGLHipSpmmPolicy* in) {
   p.tier_min_rows = in->tier_min_rows;
   p.pad_min_bytes = in->pad_min_bytes;
   p.column_parts = in->column_parts;
+  p.ids_wide = in->ids_wide;
   set_spmm_policy(p);
   API_END();
 }

@@ -53,6 +53,7 @@ struct SpmmPolicy {
   int64_t tier_min_rows = 1 << 16;
   int64_t pad_min_bytes = 4 << 20;
   int column_parts = 2;            // blocked items over column halves (gspmm_items_columns_kernel), or 1
+  int ids_wide = 0;                // 1: the column halves read int32 ids (0: 16-bit block-local ids where they apply)
 };
 
 SpmmPolicy spmm_policy();
@@ -82,6 +83,13 @@ struct BlockedPlan {
   std::vector<BlockItems> launches;  // B blocks, then the suffix if any
   rt::NDArray indices;               // int32[nnz]: column ids in plan order
   rt::NDArray pos;                   // int32[nnz]: the CSR slot of each plan slot
+  // 16-bit ids local to each launch's source block (built when bs <= 65,536;
+  // 2 B per slot beside indices): slot s of block launch l holds column -
+  // (lo + l * bs), a suffix slot column - lo truncated to 16 bits (exact, and
+  // read, only where the whole span is <= 65,536 columns)
+  rt::NDArray ids16;                 // uint16[nnz] (stored as 16-bit integers), or none
+  bool has_ids16 = false;
+  int64_t lo = 0, bs = 1, span = 0;  // the split's first column, columns per block, hi - lo
   rt::NDArray absent;                // int32 rows the first launch does not list
   int64_t n_absent = 0;
   // lazily, per edge layout: plan slot -> edge-value row (int64[nnz])
@@ -286,11 +294,13 @@ void plan_block_walk_device(int64_t R, const int64_t* indptr, const int32_t* ind
                             int64_t bs, int B, int32_t* counts, int64_t* pend, hipStream_t s);
 // the scatter into plan order: prefix slot k of row r in block b (run start
 // s) goes to item_start[r * B + b] + (k - s); suffix slot k to
-// sfx_start[r] + (k - pend[r])
+// sfx_start[r] + (k - pend[r]). out_ids16 (may be null): the slot's column
+// less its block's first (lo + b * bs; a suffix slot's less lo), 16 bits
 void plan_block_scatter_device(int64_t R, const int64_t* indptr, const int32_t* indices,
                                int64_t lo, int64_t bs, int B, const int64_t* pend,
                                const int64_t* item_start, const int64_t* sfx_start,
-                               int32_t* out_indices, int32_t* out_pos, hipStream_t s);
+                               int32_t* out_indices, int32_t* out_pos, uint16_t* out_ids16,
+                               hipStream_t s);
 // tier item i: cols[sp[i] + j] = indices[indptr[rows[i]] + j], j < sp[i+1] - sp[i]
 void plan_tier_cols_device(int64_t n, const int32_t* rows, const int64_t* indptr,
                            const int32_t* indices, const int64_t* sp, int32_t* cols,
@@ -323,5 +333,17 @@ void gspmm_items_columns(int msg_op, int64_t num_items, int64_t feat_len, const 
                          int64_t ufeat_rows, int items_per_wave, int column_parts,
                          const float* efeat, int64_t efeat_len, float* out, int64_t out_rows,
                          hipStream_t stream);
+
+
+// The same launch over 16-bit ids local to its source block, rows [col_lo,
+// col_lo + block_rows) of ufeat (copy_u, fp32 rows of 128 floats, item_ptr
+// indexing ids16 as it does the plan's indices): gspmm_items_columns_kernel
+// with a descriptor over the block alone. false, nothing launched: the gate
+// declined (items_columns_ids16_applies), the caller runs the int32 launch.
+bool gspmm_items_columns_ids16(int64_t num_items, const int32_t* item_rows,
+                               const int64_t* item_ptr, int accumulate, const uint16_t* ids16,
+                               int64_t col_lo, int64_t block_rows, const float* ufeat,
+                               int64_t ufeat_ld, int64_t ufeat_rows, float* out, int64_t out_rows,
+                               hipStream_t stream);
 
 }  // namespace dglhip

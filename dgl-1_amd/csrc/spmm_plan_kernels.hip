@@ -125,7 +125,7 @@ __global__ __launch_bounds__(256) void block_scatter_kernel(
     int64_t R, const int64_t* __restrict__ indptr, const int32_t* __restrict__ ind, int64_t lo,
     int64_t bs, int B, const int64_t* __restrict__ pend, const int64_t* __restrict__ item_start,
     const int64_t* __restrict__ sfx_start, int32_t* __restrict__ out_ind,
-    int32_t* __restrict__ out_pos) {
+    int32_t* __restrict__ out_pos, uint16_t* __restrict__ out_ids16) {
   const int64_t r = block_linear() * 4 + (threadIdx.x >> 6);
   if (r >= R) return;
   const int lane = threadIdx.x & 63;
@@ -147,12 +147,16 @@ __global__ __launch_bounds__(256) void block_scatter_kernel(
     const int64_t s = le ? base + 63 - __builtin_clzll(le) : run_s;
     if (inpre) {
       const int64_t dst = ist[b] + (k - s);
-      out_ind[dst] = ind[k];
+      const int32_t c = ind[k];
+      out_ind[dst] = c;
       out_pos[dst] = static_cast<int32_t>(k);
+      if (out_ids16) out_ids16[dst] = static_cast<uint16_t>(c - (lo + b * bs));
     } else if (valid) {
       const int64_t dst = sfx_start[r] + (k - pe);
-      out_ind[dst] = ind[k];
+      const int32_t c = ind[k];
+      out_ind[dst] = c;
       out_pos[dst] = static_cast<int32_t>(k);
+      if (out_ids16) out_ids16[dst] = static_cast<uint16_t>(c - lo);
     }
     if (stm) run_s = base + 63 - __builtin_clzll(stm);
     prev = __shfl(b, 63, 64);
@@ -282,10 +286,11 @@ void plan_block_walk_device(int64_t R, const int64_t* indptr, const int32_t* ind
 void plan_block_scatter_device(int64_t R, const int64_t* indptr, const int32_t* indices,
                                int64_t lo, int64_t bs, int B, const int64_t* pend,
                                const int64_t* item_start, const int64_t* sfx_start,
-                               int32_t* out_indices, int32_t* out_pos, hipStream_t s) {
+                               int32_t* out_indices, int32_t* out_pos, uint16_t* out_ids16,
+                               hipStream_t s) {
   if (R == 0) return;
   hipLaunchKernelGGL(block_scatter_kernel, wave_grid(R), dim3(256), 0, s, R, indptr, indices, lo,
-                     bs, B, pend, item_start, sfx_start, out_indices, out_pos);
+                     bs, B, pend, item_start, sfx_start, out_indices, out_pos, out_ids16);
   check_launch("plan block scatter");
 }
 

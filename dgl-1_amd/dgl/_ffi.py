@@ -159,6 +159,9 @@ def _load():
         "dglhip_gspmm_items_columns_device": (_c_int, [_c_int, _c_i64, _c_i64, _vp, _vp, _c_int,
                                                        _vp, _vp, _vp, _c_i64, _c_i64, _c_int,
                                                        _c_int, _vp, _c_i64, _vp, _vp]),
+        "dglhip_gspmm_items_ids16_device": (_c_int, [_c_i64, _vp, _vp, _c_int, _vp, _c_i64,
+                                                     _c_i64, _vp, _c_i64, _c_i64, _vp, _c_i64,
+                                                     _vp]),
         "dglhip_gspmm_items_kernel": (_c_int, [_c_int, _c_i64, _c_i64, _c_i64, _c_i64, _c_int,
                                                _c_int, _vp, _vp, _vp]),
         "dglhip_gspmm_items_columns_ids_cap": (_c_int, []),

@@ -153,14 +153,20 @@ class _PlanLaunch(object):
     arrays): ``rows`` (int32) the rows with slots in the block, longest first
     (stable by row id); item i's slots are [ptr[i], ptr[i+1]) of the plan's
     global slot arrays (``ptr`` holds global offsets); ``indices`` / ``pos``
-    this launch's slots (column ids, and the CSR slot each came from)."""
-    __slots__ = ("rows", "ptr", "indices", "pos", "nnz", "off", "suffix")
+    this launch's slots (column ids, and the CSR slot each came from);
+    ``col_lo`` the first column of the launch's source block (the suffix: of
+    the whole span) and ``ids16`` its slots' 16-bit ids local to it, as an
+    int16 view of the bits (None where the plan has none)."""
+    __slots__ = ("rows", "ptr", "indices", "pos", "nnz", "off", "suffix", "col_lo", "ids16")
 
 
 class _BlockedSchedule(list):
     """The plan's source-blocked schedule: its launches (B blocks, then the
     suffix if any) plus the global arrays: ``indices`` / ``pos`` (plan
-    order), ``absent`` (rows the first launch does not list)."""
+    order), ``absent`` (rows the first launch does not list), ``lo`` / ``bs``
+    / ``span`` (the first referenced column, columns per block, columns
+    referenced) and ``ids16`` (the uint16 block-local ids of every slot as an
+    int16 tensor of the same bits, built when ``bs`` <= 65,536, else None)."""
 
 
 def _blocked_native(csr, row_bytes, block_bytes, blocks=0):
@@ -180,6 +186,8 @@ def _blocked_native(csr, row_bytes, block_bytes, blocks=0):
         res = _BlockedSchedule()
         res.indices, res.pos, res.absent = f(1), f(2), f(3)
         res.B, res.has_suffix = int(B), bool(sfx)
+        res.lo, res.bs, res.span, has16 = (int(x) for x in meta[4 + 4 * int(L):8 + 4 * int(L)])
+        res.ids16 = f(4 + 2 * int(L)) if has16 else None
         for i in range(int(L)):
             n_items, nnz, off, suffix = meta[4 + 4 * i:8 + 4 * i]
             it = _PlanLaunch()
@@ -187,6 +195,8 @@ def _blocked_native(csr, row_bytes, block_bytes, blocks=0):
             it.indices = res.indices[off:off + nnz]
             it.pos = res.pos[off:off + nnz]
             it.nnz, it.off, it.suffix = int(nnz), int(off), bool(suffix)
+            it.col_lo = res.lo if it.suffix else res.lo + i * res.bs
+            it.ids16 = None if res.ids16 is None else res.ids16[off:off + nnz]
             res.append(it)
     plan._cache[key] = res
     return res

@@ -70,10 +70,10 @@ class _Policy(ctypes.Structure):
                 ("block_min_slots", ctypes.c_int64), ("block_max_stretch", ctypes.c_double),
                 ("block_max_suffix", ctypes.c_double), ("block_min_row_bytes", ctypes.c_int64),
                 ("tier_min_rows", ctypes.c_int64), ("pad_min_bytes", ctypes.c_int64),
-                ("column_parts", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+                ("column_parts", ctypes.c_int32), ("ids_wide", ctypes.c_int32)]
 
 
-_POLICY_KEYS = tuple(n for n, _ in _Policy._fields_ if n != "reserved")
+_POLICY_KEYS = tuple(n for n, _ in _Policy._fields_)
 # bumped at every policy change: part of the keys of the Python-side caches
 # of native plan structures (a new policy may give a CSR another schedule)
 _POLICY_GEN = [0]
@@ -85,7 +85,9 @@ def schedule_policy():
     blocked schedule's items a wave takes), block_bytes, block_table_min,
     block_table_max, block_min_slots, block_max_stretch, block_max_suffix,
     block_min_row_bytes, tier_min_rows, pad_min_bytes, column_parts (1, or 2:
-    those launches over column halves, one half per XCD))."""
+    those launches over column halves, one half per XCD), ids_wide (0: the
+    column halves read 16-bit ids local to the launch's source block where a
+    block has at most 65,536 rows, 1: always int32 ids))."""
     p = _Policy()
     check_call(LIB.dglhip_spmm_get_policy(ctypes.addressof(p)))
     return {k: getattr(p, k) for k in _POLICY_KEYS}

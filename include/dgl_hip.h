@@ -311,10 +311,10 @@ typedef struct DGLHipSpmmPlanObj* DGLHipSpmmPlan;
  * pad_rows 1, items_per_wave 2, block_bytes 6 MiB, block_table_min 16 MiB, block_table_max
  * 256 MiB, block_min_slots 12, block_max_stretch 3, block_max_suffix 1/16,
  * block_min_row_bytes 128, tier_min_rows 65536, pad_min_bytes 4 MiB,
- * column_parts 2; the
+ * column_parts 2, ids_wide 0; the
  * environment variables DGLHIP_ROW_SPLIT / _BLOCKED / _BLOCK_BYTES /
  * _BLOCK_MIN_SLOTS / _BLOCK_MAX_STRETCH / _SHORT_ROWS / _PAD_ROWS /
- * _ITEMS_PER_WAVE / _COLUMN_PARTS set the
+ * _ITEMS_PER_WAVE / _COLUMN_PARTS / _IDS_WIDE set the
  * initial values. Results never depend on it beyond the documented
  * tolerance of the heavy-row split (re-association of a chunked row). */
 typedef struct {
@@ -332,7 +332,9 @@ typedef struct {
   int64_t tier_min_rows;                     /* short rows needed to tier */
   int64_t pad_min_bytes;                     /* tables smaller than this: no padding */
   int32_t column_parts;   /* 2: the pair kernel's launches over column halves, one per XCD; or 1 */
-  int32_t reserved;       /* 0 */
+  int32_t ids_wide;       /* 0: the column halves read 16-bit ids local to the launch's source
+                             block where they apply (blocks of at most 65,536 rows); 1: always
+                             int32 ids. The word was `reserved` (0) before. */
 } DGLHipSpmmPolicy;
 int dglhip_spmm_get_policy(DGLHipSpmmPolicy* out);
 int dglhip_spmm_set_policy(const DGLHipSpmmPolicy* policy);
@@ -1055,6 +1057,20 @@ int dglhip_gspmm_items_columns_device(int msg_op, int64_t num_items, int64_t fea
                                       const float* ufeat, int64_t ufeat_ld, int64_t ufeat_rows,
                                       int items_per_wave, int column_parts, const float* efeat,
                                       int64_t efeat_len, float* out, void* stream);
+/* The column-half launch over 16-bit ids local to its source block: copy_u
+ * over fp32 rows of 128 floats, slot s of item i (item_ptr as above, indexing
+ * ids16) gathers row col_lo + ids16[s] of ufeat, ids16[s] < block_rows <=
+ * 65,536. The kernel's table is the block alone, rows [col_lo, col_lo +
+ * block_rows) of the ufeat_rows, so the block, not the table, has to end
+ * 1 KiB below 4 GiB. The launch plan runs its blocks through this (policy
+ * word ids_wide 0); the entry is for tests. Operands that do not take the
+ * kernel (alignment, sizes, a block past the table) are an error. The same
+ * bits as the entries above give over col_lo + ids16[s]. */
+int dglhip_gspmm_items_ids16_device(int64_t num_items, const int32_t* item_rows,
+                                    const int64_t* item_ptr, int accumulate,
+                                    const uint16_t* ids16, int64_t col_lo, int64_t block_rows,
+                                    const float* ufeat, int64_t ufeat_ld, int64_t ufeat_rows,
+                                    float* out, int64_t out_rows, void* stream);
 /* Which kernel a launch of items with these operands takes: *kernel = 0 one
  * item per wave, 1 two items per wave, 2 four items per wave over a column
  * half (out_rows: the rows of out, 0: not known, as the entry above passes).
