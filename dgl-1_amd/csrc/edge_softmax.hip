@@ -43,6 +43,7 @@
 #include "../../include/dgl_hip.h"
 #include "common.h"
 #include "launch.h"
+#include "row_pieces.h"
 
 #include <hip/hip_runtime.h>
 
@@ -79,33 +80,8 @@ __device__ __forceinline__ void store_cols(float* p, const float (&v)[V]) {
   }
 }
 
-__device__ __forceinline__ int64_t clampi(int64_t v, int64_t lo, int64_t hi) {
-  return v < lo ? lo : (v > hi ? hi : v);
-}
-
 // torch's max: a NaN on either side wins (fmaxf would drop it)
 __device__ __forceinline__ float nanmax(float a, float b) { return (a > b || a != a) ? a : b; }
-
-// The row that holds `slot`: the smallest r with indptr[r + 1] > slot (R if
-// none), found by the whole wave: every round its 64 lanes probe the range at
-// even steps and a ballot keeps the step that holds the answer, so 2^18 rows
-// take three dependent loads instead of eighteen. Every lane must call it.
-__device__ __forceinline__ int64_t row_of(const int64_t* __restrict__ indptr, int64_t R,
-                                          int64_t slot, int lane) {
-  int64_t lo = 0, hi = R;  // the answer is in [lo, hi]
-  while (lo < hi) {
-    const int64_t step = (hi - lo + 63) >> 6;
-    int64_t r = lo + (lane + 1) * step - 1;  // the last row of this lane's step
-    if (r > hi - 1) r = hi - 1;
-    const unsigned long long above = __ballot(indptr[r + 1] > slot);
-    if (above == 0) return hi;
-    const int j = __ffsll(above) - 1;
-    const int64_t rj = lo + (j + 1) * step - 1;
-    hi = rj > hi - 1 ? hi - 1 : rj;
-    lo = lo + j * step;
-  }
-  return lo;
-}
 
 struct Args {
   int64_t R, nnz, H;
@@ -387,22 +363,8 @@ __global__ __launch_bounds__(kThreads) void edge_softmax_rows_kernel(Args a) {
 // first piece, where the combined result is left. The same in every lane.
 __device__ __forceinline__ bool piece_of(const Args& a, int64_t item, int lane, int64_t& k0,
                                          int64_t& k1, int64_t& first) {
-  const int64_t g = item >> 1;
-  const bool inner = item & 1;
-  const int64_t b0 = g * kChunk;
-  if (g >= a.G || b0 >= a.nnz) return false;
-  const int64_t b1 = b0 + kChunk < a.nnz ? b0 + kChunk : a.nnz;
-  const int64_t r = row_of(a.indptr, a.R, inner ? b1 - 1 : b0, lane);
-  if (r >= a.R) return false;
-  const int64_t beg = clampi(a.indptr[r], 0, a.nnz);
-  const int64_t end = clampi(a.indptr[r + 1], beg, a.nnz);
-  if (end - beg <= kChunk) return false;
-  if (inner ? beg <= b0 : beg > b0) return false;
-  k0 = beg > b0 ? beg : b0;
-  k1 = end < b1 ? end : b1;
-  const int64_t g0 = beg / kChunk;
-  first = 2 * g0 + (beg > g0 * kChunk ? 1 : 0);
-  return k0 < k1;
+  int64_t r, last;
+  return long_row_piece(a.indptr, a.R, a.nnz, a.G, kChunk, item, lane, r, k0, k1, first, last);
 }
 
 // A piece is a workgroup's, a quarter of the block's slots per wave, so at

@@ -235,6 +235,15 @@ def _load():
                                            [_c_i64, _vp, _vp]),
         "dglhip_edge_softmax_host": (_c_int, [_c_i64, _c_i64, _c_i64] + [_vp] * 4 + [_c_int]),
         "dglhip_edge_softmax_bwd_host": (_c_int, [_c_i64, _c_i64, _c_i64] + [_vp] * 5 + [_c_int]),
+        "dglhip_dot_attention_workspace_bytes": (_c_i64, [_c_i64] * 5),
+        "dglhip_dot_attention_device": (_c_int, [_c_i64] * 5 + [_vp] * 6 + [_c_float] * 3 +
+                                        [_vp, _vp, _c_i64, _vp, _vp]),
+        "dglhip_dot_attention_bwd_device": (_c_int, [_c_i64] * 5 + [_vp] * 12 + [_c_float] * 3 +
+                                            [_vp] * 4 + [_c_i64, _c_i64, _vp, _vp]),
+        "dglhip_dot_attention_host": (_c_int, [_c_i64] * 5 + [_vp] * 5 + [_c_float] * 3 +
+                                      [_vp, _vp, _c_int]),
+        "dglhip_dot_attention_bwd_host": (_c_int, [_c_i64] * 5 + [_vp] * 10 + [_c_float] * 3 +
+                                          [_vp] * 4 + [_c_int]),
         "dglhip_induced_subgraph_workspace_bytes": (_c_i64, [_c_i64, _c_i64, _c_i64]),
         "dglhip_induced_subgraph_count_device": (_c_int, [_c_i64, _c_i64, _c_i64, _vp, _vp, _vp,
                                                           _vp, _c_i64, _vp, _vp]),

@@ -1,7 +1,8 @@
 """The edge-attention operators: GAT's per-edge attention, its fused
 aggregation layer with its backwards and its attention logits
-(csrc/gat_fused.hip), and the softmax over a node's edges
-(csrc/edge_softmax.hip)."""
+(csrc/gat_fused.hip), the softmax over a node's edges
+(csrc/edge_softmax.hip) and the fused scaled dot-product attention
+(csrc/dot_attention.hip)."""
 from __future__ import absolute_import
 
 import os
@@ -19,7 +20,7 @@ from .policy import MSG_U_MUL_E, MSG_COPY_E, RED_SUM, SLOT, schedule_policy
 from .plan import _block_cuts, _block_edge_rows, _block_plan, _cuts_native
 from .spmm import (
     _eid_major, _f32c, _fwd_slot_of_bwd, _operand_rows, _run_gspmm, _run_sddmm_dot,
-    edge_order_of, gspmm_ranges)
+    edge_order_of, gspmm, gspmm_ranges)
 
 # ---------------------------------------------------------------------------
 # GAT edge attention (fused u_add_v g-SDDMM + leaky_relu + exp + clamp)
@@ -635,3 +636,157 @@ def segment_softmax(x, segments):
         return torch.empty_like(x)
     rows = (segments.num_segments, segments.on(x.device), None, None, segments.max_rows)
     return _EdgeSoftmax.apply(x2, rows).view(x.shape)
+
+
+# ---------------------------------------------------------------------------
+# Scaled dot-product attention over the edges, fused (csrc/dot_attention.hip)
+# ---------------------------------------------------------------------------
+DOT_ATTENTION_CHUNK = 1024  # DGLHIP_DOT_ATTENTION_CHUNK: a longer row is cut into pieces
+DOT_ATTENTION_BATCH = 8  # DGLHIP_DOT_ATTENTION_BATCH: slots per rescale of the running sums
+
+
+def _dot_attention_vec(D, tensors):
+    """Floats per access of the fused kernels (their gate: dot_attention.hip)."""
+    V = 4 if D % 4 == 0 else (2 if D % 2 == 0 else 1)
+    for t in tensors:
+        while V > 1 and t.data_ptr() % (4 * V):
+            V >>= 1
+    return V
+
+
+def _dot_attention_workspace(csrs, H, D, dev):
+    nbytes = max(LIB.dglhip_dot_attention_workspace_bytes(c.num_rows, c.nnz, H, D, c.max_degree)
+                 for c in csrs)
+    return _workspace(nbytes, dev) if nbytes else None
+
+
+class _DotAttention(torch.autograd.Function):
+    """out = softmax over each destination's in-edges of clamp(<q, k> * scale)
+    times v, in one pass; the backward recomputes the scores from q, k and
+    the saved lse: dq over the CSR, dk and dv over its transpose. Saves q, k,
+    v, out and lse (rows, H): nothing per edge."""
+
+    @staticmethod
+    def forward(ctx, adj, scale, lo, hi, q, k, v):
+        fwd = adj.fwd
+        R, H, D = q.shape
+        dev = q.device
+        out = torch.empty_like(q)
+        lse = torch.empty(R, H, dtype=torch.float32, device=dev)
+        head = (R, fwd.num_cols, fwd.nnz, H, D, ptr(fwd.indptr), ptr(fwd.indices))
+        if dev.type == "cuda":
+            ws = _dot_attention_workspace((fwd,), H, D, dev)
+            check_call(LIB.dglhip_dot_attention_device(*(head + (
+                ptr(fwd.row_order), ptr(q), ptr(k), ptr(v), scale, lo, hi, ptr(out), ptr(lse),
+                fwd.max_degree, ptr(ws), _stream_of(dev)))))
+        else:
+            check_call(LIB.dglhip_dot_attention_host(*(head + (
+                ptr(q), ptr(k), ptr(v), scale, lo, hi, ptr(out), ptr(lse), 0))))
+        ctx.adj, ctx.scale, ctx.lo, ctx.hi = adj, scale, lo, hi
+        ctx.save_for_backward(q, k, v, out, lse)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, k, v, out, lse = ctx.saved_tensors
+        fwd, bwd = ctx.adj.fwd, ctx.adj.bwd
+        R, H, D = q.shape
+        dev = q.device
+        dout = _f32c(dout)
+        if dout.data_ptr() % 16:
+            # a gradient that arrives as a view at an odd offset would narrow
+            # the accesses below what the forward's gate found for this D
+            dout = dout.clone()
+        delta = torch.empty_like(lse)
+        dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+        head = (R, fwd.num_cols, fwd.nnz, H, D, ptr(fwd.indptr), ptr(fwd.indices))
+        mid = (ptr(q), ptr(k), ptr(v), ptr(out), ptr(lse), ptr(dout), ctx.scale, ctx.lo, ctx.hi,
+               ptr(delta), ptr(dq), ptr(dk), ptr(dv))
+        if dev.type == "cuda":
+            ws = _dot_attention_workspace((fwd, bwd), H, D, dev)
+            check_call(LIB.dglhip_dot_attention_bwd_device(*(
+                head + (ptr(fwd.row_order), ptr(bwd.indptr), ptr(bwd.indices),
+                        ptr(bwd.row_order)) + mid +
+                (fwd.max_degree, bwd.max_degree, ptr(ws), _stream_of(dev)))))
+        else:
+            check_call(LIB.dglhip_dot_attention_bwd_host(*(
+                head + (ptr(bwd.indptr), ptr(bwd.indices)) + mid + (0,))))
+        return None, None, None, None, dq, dk, dv
+
+
+class _SlotDot(torch.autograd.Function):
+    """s[k, h] = <q[row of slot k, h], k[column of slot k, h]> in forward slot
+    order (the g-SDDMM dot) with its backward, two u_mul_e products: the
+    composed attention's first step."""
+
+    @staticmethod
+    def forward(ctx, adj, H, q2, k2):
+        ctx.adj, ctx.H = adj, H
+        ctx.save_for_backward(q2, k2)
+        return _run_sddmm_dot(adj.fwd, q2, k2, adj.fwd.nnz, H, slot=True)
+
+    @staticmethod
+    def backward(ctx, ds):
+        q2, k2 = ctx.saved_tensors
+        adj, H, F = ctx.adj, ctx.H, q2.shape[1]
+        ds = _f32c(ds)
+        dq, _ = _run_gspmm(adj.fwd, MSG_U_MUL_E, RED_SUM, k2, ds, H, F, False, emap=SLOT)
+        dk, _ = _run_gspmm(adj.bwd, MSG_U_MUL_E, RED_SUM, q2, ds, H, F, False,
+                           emap=_fwd_slot_of_bwd(adj))
+        return None, None, dq, dk
+
+
+def _dot_attention_composed(adj, q, k, v, scale, clamp):
+    """The attention from the three operators it fuses, every edge tensor in
+    forward slot order: heads wider than the fused kernels' lane map."""
+    R, H, D = q.shape
+    s = _SlotDot.apply(adj, H, q.reshape(R, H * D), k.reshape(k.shape[0], H * D)) * scale
+    if clamp is not None:
+        s = torch.clamp(s, clamp[0], clamp[1])
+    a = edge_softmax(adj, s, "dst", "slot")
+    return gspmm(adj, "u_mul_e", "sum", v, a.unsqueeze(-1), edge_order="slot")
+
+
+def dot_attention(adj, q, k, v, scale=None, clamp=None):
+    """Scaled dot-product attention over the edges of ``adj`` (the transformer
+    example's src_dot_dst / scaled_exp / two sums / wv / z,
+    examples/pytorch/transformer/modules/models.py:79-86): for every
+    destination r, head h and in-edge j from source u_j,
+
+        s_j = <q[r, h], k[u_j, h]> * scale       (scale None: D ** -0.5)
+        s_j = min(max(s_j, lo), hi)              (clamp=(lo, hi) only)
+        out[r, h] = sum_j softmax_j(s) v[u_j, h]
+
+    q (num_rows, H, D), k and v (num_cols, H, D) float32; returns (num_rows,
+    H, D), differentiable in q, k and v (a clamped score passes no gradient
+    when strictly outside the bounds, as torch.clamp). A destination without
+    in-edges gets zeros and passes no gradient. One kernel forward, two
+    backward (csrc/dot_attention.hip): no tensor of the size of the edge set
+    is stored or kept for the backward, only out and a (num_rows, H)
+    log-sum-exp. No atomics: the same bits on every call. NaN and infinities
+    follow edge_softmax's rules per (destination, head). Heads wider than
+    64 * V (V floats per access: 4 when D % 4 == 0 and the tensors are
+    16-byte aligned, else 2, else 1) run as the composition gsddmm_dot,
+    torch.clamp, edge_softmax, gspmm."""
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 3:
+            raise DGLError("dot_attention: %s must be a (rows, heads, features) tensor" % name)
+    if k.shape != v.shape or q.shape[1:] != k.shape[1:]:
+        raise DGLError("dot_attention: q %s, k %s and v %s differ in heads or features"
+                       % (tuple(q.shape), tuple(k.shape), tuple(v.shape)))
+    if clamp is not None and not float(clamp[0]) <= float(clamp[1]):
+        raise DGLError("dot_attention: clamp bounds %r are not ordered" % (clamp,))
+    dev = q.device
+    adj = adj.to(dev)
+    if q.shape[0] != adj.shape[0] or k.shape[0] != adj.shape[1]:
+        raise DGLError("dot_attention: %d rows of q and %d of k, v for a %d x %d adjacency"
+                       % (q.shape[0], k.shape[0], adj.shape[0], adj.shape[1]))
+    q, k, v = _f32c(q), _f32c(k), _f32c(v)
+    D = q.shape[2]
+    if q.numel() == 0 or adj.fwd.nnz == 0:
+        return torch.zeros_like(q)
+    scale = float(D) ** -0.5 if scale is None else float(scale)
+    if D > 64 * _dot_attention_vec(D, (q, k, v)):
+        return _dot_attention_composed(adj, q, k, v, scale, clamp)
+    lo, hi = (-float("inf"), float("inf")) if clamp is None else (float(clamp[0]), float(clamp[1]))
+    return _DotAttention.apply(adj, scale, lo, hi, q, k, v)

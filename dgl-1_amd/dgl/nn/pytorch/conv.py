@@ -9,6 +9,8 @@ the later-DGL module names and arguments) on top of:
 * GraphConv    : update_all(copy_src, sum) -> one g-SpMM (gcn_spmv.py:45-62)
 * GATConv      : attention, dropout, per-head weighted sum and copy_edge
                  normaliser in one kernel (gat/train.py:61-96, kernel.gat_aggregate)
+* DotGatConv   : scaled dot-product attention over the in-edges in one kernel
+                 (transformer/modules/models.py:79-86, kernel.dot_attention)
 * SAGEConv     : update_all(copy_src, mean) -> g-SpMM mean
 * RelGraphConv : typed-edge block-diagonal g-SpMM (rgcn/layers.py:121-132)
 """
@@ -23,7 +25,7 @@ from ... import kernel
 from ...base import DGLError
 from .linear import NodeLinear, sage_dense, bias_add
 
-__all__ = ["GraphConv", "GATConv", "SAGEConv", "RelGraphConv"]
+__all__ = ["GraphConv", "GATConv", "DotGatConv", "SAGEConv", "RelGraphConv"]
 
 
 class GraphConv(nn.Module):
@@ -105,6 +107,24 @@ class GATConv(nn.Module):
         if self.res_fc is not None:
             rst = rst + self.res_fc(h).view(-1, self.num_heads, self.out_feats)
         return self.activation(rst) if self.activation else rst
+
+
+class DotGatConv(nn.Module):
+    """Multi-head dot-product graph attention: one projection to num_heads *
+    out_feats, each node's projected row its query, key and value over its
+    in-edges, scores scaled by out_feats ** -0.5; returns (N, num_heads,
+    out_feats)."""
+
+    def __init__(self, in_feats, out_feats, num_heads):
+        super(DotGatConv, self).__init__()
+        self.num_heads, self.out_feats = num_heads, out_feats
+        self.fc = nn.Linear(in_feats, num_heads * out_feats, bias=False)
+        nn.init.xavier_normal_(self.fc.weight, gain=nn.init.calculate_gain("relu"))
+
+    def forward(self, g, feat):
+        ft = self.fc(feat).view(-1, self.num_heads, self.out_feats)
+        return kernel.dot_attention(g.sparse_adjacency(feat.device), ft, ft, ft,
+                                    scale=self.out_feats ** -0.5)
 
 
 class SAGEConv(nn.Module):

@@ -1,11 +1,12 @@
 """Softmax over the edges of each node (the ``edge_softmax`` later releases of
 the reference added to ``dgl.nn.pytorch``): one HIP kernel forward and one
-backward (``kernel.edge_softmax``, csrc/edge_softmax.hip)."""
+backward (``kernel.edge_softmax``, csrc/edge_softmax.hip), and the fused
+scaled dot-product attention over them (``kernel.dot_attention``)."""
 from __future__ import absolute_import
 
 from ... import kernel
 
-__all__ = ["edge_softmax"]
+__all__ = ["edge_softmax", "dot_attention"]
 
 
 def edge_softmax(graph, logits, norm_by="dst"):
@@ -22,3 +23,20 @@ def edge_softmax(graph, logits, norm_by="dst"):
     >>> g.update_all(fn.src_mul_edge("v", "a", "m"), fn.sum("m", "o"))
     """
     return kernel.edge_softmax(graph.sparse_adjacency(logits.device), logits, norm_by)
+
+
+def dot_attention(graph, q, k, v, scale=None, clamp=None):
+    """Scaled dot-product attention over the edges of ``graph``: every node
+    attends over its in-edges, ``out[n, h] = sum_j softmax_j(<q[n, h], k[u_j,
+    h]> * scale) v[u_j, h]`` (``scale`` None: ``D ** -0.5``; ``clamp=(lo, hi)``
+    bounds the scaled scores first, the transformer example's
+    ``clamp(-10, 10)``). ``q``, ``k``, ``v`` are ``(N, H, D)`` float32 node
+    tensors; returns ``(N, H, D)``, differentiable in all three, a node
+    without in-edges gets zeros. One fused HIP kernel forward and two backward
+    (``kernel.dot_attention``, csrc/dot_attention.hip): no per-edge tensor is
+    made.
+
+    >>> out = dot_attention(g, q, k, v)             # instead of gsddmm_dot,
+    ...                                             # edge_softmax, update_all
+    """
+    return kernel.dot_attention(graph.sparse_adjacency(q.device), q, k, v, scale, clamp)

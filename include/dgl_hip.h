@@ -589,6 +589,80 @@ int dglhip_edge_softmax_bwd_host(int64_t num_rows, int64_t nnz, int64_t feat_len
                                  const float* dy, float* dx, int num_threads);
 
 /* ------------------------------------------------------------------------ */
+/* Scaled dot-product attention over a graph's edges, fused                  */
+/* (csrc/dot_attention.hip, csrc/dot_attention_host.cc). The CSR's rows are  */
+/* the num_rows destinations, its columns the num_cols sources: indptr       */
+/* int64[num_rows + 1], indices int32[nnz]. q: float32 [num_rows, H, D]; k,  */
+/* v: [num_cols, H, D], all packed. Per row r, head h and slot j (source     */
+/* u_j), in float32:                                                         */
+/*   s_j = <q[r,h,:], k[u_j,h,:]> * scale, then min(max(s_j, lo), hi)        */
+/*         (-inf, +inf: no clamp),                                           */
+/*   a_j = expf(s_j - m) / l, m = max_j s_j, l = sum_j expf(s_j - m),        */
+/*   out[r,h,:] = sum_j a_j v[u_j,h,:], lse[r,h] = m + logf(l).              */
+/* A row without slots stores zeros in out and 0 in lse. NaN and infinities  */
+/* follow the edge softmax's rules per (row, head) group.                    */
+/* Backward, from dout [num_rows, H, D] and the forward's out and lse, with  */
+/* delta[r,h] = <dout[r,h,:], out[r,h,:]> (written, [num_rows, H]):          */
+/*   a_j = expf(s_j - lse), dp_j = <dout[r,h,:], v[u_j,h,:]>,                */
+/*   ds_j = a_j (dp_j - delta), 0 where s_j was strictly outside [lo, hi],   */
+/*   dq[r] = sum_j ds_j scale k[u_j], dk[u] = sum ds_j scale q[r],           */
+/*   dv[u] = sum a_j dout[r], the last two over the transposed CSR (t_*:     */
+/*   rows = sources, indices = destinations).                                */
+/* Nothing of nnz entries is stored or allocated; no atomics, every output   */
+/* element has one writer, the same bits on every call. The device forms     */
+/* serve head_dim <= 64 V, V the floats per access (4 when head_dim % 4 == 0 */
+/* and every tensor is 16-byte aligned, else 2 by the same rule, else 1),    */
+/* and return -1 beyond. A row (a source, in the transposed half) of more    */
+/* than DGLHIP_DOT_ATTENTION_CHUNK slots is cut where it crosses the         */
+/* multiples of that many slots, a piece a wave, combined through            */
+/* `workspace` in slot order. Slots run in batches of                        */
+/* DGLHIP_DOT_ATTENTION_BATCH, one rescale of the running sums per batch.    */
+/* ------------------------------------------------------------------------ */
+#define DGLHIP_DOT_ATTENTION_CHUNK 1024
+#define DGLHIP_DOT_ATTENTION_BATCH 8
+/* Bytes of the device forms' workspace for a CSR of nnz slots whose longest
+ * row is max_row_len (-1: not known): 0 when that is known and at most the
+ * chunk. The backward needs the larger of its two CSRs' sizes. */
+int64_t dglhip_dot_attention_workspace_bytes(int64_t num_rows, int64_t nnz, int64_t num_heads,
+                                             int64_t head_dim, int64_t max_row_len);
+/* Device forms: all pointers are device pointers. row_order (int32 per row or
+ * NULL) only schedules the launch. Launch sizes come from the sizes and
+ * max_row_len / max_col_len (the longest row of the CSR / of the transposed
+ * one, -1 if not known) alone: no host sync, no allocation. indptr entries
+ * are clamped to [0, nnz] and column ids to the columns, never followed
+ * beyond. */
+int dglhip_dot_attention_device(int64_t num_rows, int64_t num_cols, int64_t nnz,
+                                int64_t num_heads, int64_t head_dim, const int64_t* indptr,
+                                const int32_t* indices, const int32_t* row_order, const float* q,
+                                const float* k, const float* v, float scale, float lo, float hi,
+                                float* out, float* lse, int64_t max_row_len, void* workspace,
+                                void* stream);
+int dglhip_dot_attention_bwd_device(int64_t num_rows, int64_t num_cols, int64_t nnz,
+                                    int64_t num_heads, int64_t head_dim, const int64_t* indptr,
+                                    const int32_t* indices, const int32_t* row_order,
+                                    const int64_t* t_indptr, const int32_t* t_indices,
+                                    const int32_t* t_row_order, const float* q, const float* k,
+                                    const float* v, const float* out, const float* lse,
+                                    const float* dout, float scale, float lo, float hi,
+                                    float* delta, float* dq, float* dk, float* dv,
+                                    int64_t max_row_len, int64_t max_col_len, void* workspace,
+                                    void* stream);
+/* Host forms (thread pool), one sequential pass per row, any head_dim. An
+ * indptr that does not start at 0, decreases or does not end at nnz, or a
+ * column id outside the columns, returns -1 with a message. */
+int dglhip_dot_attention_host(int64_t num_rows, int64_t num_cols, int64_t nnz, int64_t num_heads,
+                              int64_t head_dim, const int64_t* indptr, const int32_t* indices,
+                              const float* q, const float* k, const float* v, float scale,
+                              float lo, float hi, float* out, float* lse, int num_threads);
+int dglhip_dot_attention_bwd_host(int64_t num_rows, int64_t num_cols, int64_t nnz,
+                                  int64_t num_heads, int64_t head_dim, const int64_t* indptr,
+                                  const int32_t* indices, const int64_t* t_indptr,
+                                  const int32_t* t_indices, const float* q, const float* k,
+                                  const float* v, const float* out, const float* lse,
+                                  const float* dout, float scale, float lo, float hi,
+                                  float* delta, float* dq, float* dk, float* dv, int num_threads);
+
+/* ------------------------------------------------------------------------ */
 /* Node-induced subgraph on the device (csrc/induced_subgraph.hip): the      */
 /* reference's Graph::VertexSubgraph (src/graph/graph.cc:441-469) over a     */
 /* source-major CSR that is already on the device: indptr int64[num_nodes +  */
