@@ -34,12 +34,11 @@
 
 #include "../../include/dgl_hip.h"
 #include "compact.h"
+#include "typed_items.h"
 
 namespace dglhip {
 
 namespace {
-
-constexpr int64_t kChunk = DGLHIP_TYPED_CHUNK;
 
 // most output slices per wave of the typed-block g-SpMM: 1 by default (one
 // wave per 64 outputs); 8 — one wave per item at R-GCN's 500 — ran the
@@ -52,28 +51,6 @@ template <int SI>
 struct EdgesInFlight {
   static constexpr int value = SI == 0 ? 4 : (SI <= 5 ? 8 : (SI <= 8 ? 4 : 2));
 };
-
-// The slot range of item `it` of the chunked rows (item_ptr: a row's first
-// item; a row of deg slots has max(1, ceil(deg / kChunk)) items) and where
-// its chain goes: the row itself when the row is one item, else the item's
-// partial row.
-// Items past the last row's (item_row[it] >= num_rows: the caller sized the
-// item list by its bound num_rows + nnz / kChunk, no host sync) do nothing.
-__device__ __forceinline__ bool item_range(int64_t it, int64_t num_rows,
-                                           const int64_t* __restrict__ ptr,
-                                           const int64_t* __restrict__ item_ptr,
-                                           const int32_t* __restrict__ item_row, int64_t* row,
-                                           int64_t* beg, int64_t* end, bool* single) {
-  const int64_t r = item_row[it];
-  if (r >= num_rows) return false;
-  const int64_t first = item_ptr[r], nit = item_ptr[r + 1] - first;
-  const int64_t b = ptr[r] + (it - first) * kChunk;
-  *row = r;
-  *beg = b;
-  *end = nit == 1 ? ptr[r + 1] : (b + kChunk < ptr[r + 1] ? b + kChunk : ptr[r + 1]);
-  *single = nit == 1;
-  return true;
-}
 
 // One wave per (item, slice of 64 * T output features): lane l of pass p
 // takes outputs p * 64 * T + 64 t + l, t < T (R-GCN's 500 features: T = 8, one
@@ -791,6 +768,17 @@ __global__ __launch_bounds__(256) void typed_nitems_kernel(int64_t num_rows,
 }
 
 }  // namespace
+
+void launch_typed_combine(int64_t num_heavy, int64_t F, const int32_t* heavy_row,
+                          const int64_t* item_ptr, const float* partial, float* out,
+                          const float* row_scale, hipStream_t stream) {
+  const int64_t total = num_heavy * F;
+  timed_launch(stream, [&] {
+    hipLaunchKernelGGL(typed_block_combine_kernel, grid_1d((total + 255) / 256), dim3(256), 0,
+                       stream, num_heavy, F, heavy_row, item_ptr, partial, out, row_scale);
+  });
+}
+
 }  // namespace dglhip
 
 using namespace dglhip;
@@ -855,13 +843,8 @@ int dglhip_typed_block_spmm_device(int64_t num_rows, int64_t num_items, int64_t 
   });
 #undef DGLHIP_TBT
 #undef DGLHIP_TB
-  if (num_heavy > 0) {
-    const int64_t total = num_heavy * Fo;
-    timed_launch(stream, [&] {
-      hipLaunchKernelGGL(typed_block_combine_kernel, grid_1d((total + 255) / 256), dim3(256), 0,
-                         stream, num_heavy, Fo, heavy_row, item_ptr, partial, out);
-    });
-  }
+  if (num_heavy > 0)
+    launch_typed_combine(num_heavy, Fo, heavy_row, item_ptr, partial, out, nullptr, stream);
   API_END();
 }
 
@@ -960,14 +943,9 @@ int dglhip_typed_msg_sum_device(int64_t num_rows, int64_t num_items, int64_t fea
     }
   });
 #undef DGLHIP_MS
-  if (num_heavy > 0) {
-    const int64_t total = num_heavy * feat_len;
-    timed_launch(stream, [&] {
-      hipLaunchKernelGGL(typed_block_combine_kernel, grid_1d((total + 255) / 256), dim3(256), 0,
-                         stream, num_heavy, feat_len, heavy_row, item_ptr, partial, out,
-                         row_scale);
-    });
-  }
+  if (num_heavy > 0)
+    launch_typed_combine(num_heavy, feat_len, heavy_row, item_ptr, partial, out, row_scale,
+                         stream);
   API_END();
 }
 
@@ -1031,13 +1009,8 @@ int dglhip_typed_block_wgrad_scaled_device(int64_t num_rels, int64_t num_items,
                          partial);
     });
   }
-  if (num_heavy > 0) {
-    const int64_t t2 = num_heavy * wr;
-    timed_launch(stream, [&] {
-      hipLaunchKernelGGL(typed_block_combine_kernel, grid_1d((t2 + 255) / 256), dim3(256), 0,
-                         stream, num_heavy, wr, heavy_rel, item_ptr, partial, dweight);
-    });
-  }
+  if (num_heavy > 0)
+    launch_typed_combine(num_heavy, wr, heavy_rel, item_ptr, partial, dweight, nullptr, stream);
   API_END();
 }
 

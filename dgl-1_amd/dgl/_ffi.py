@@ -122,6 +122,11 @@ def _load():
                                         [_vp] * 8),
         "dglhip_typed_block_wgrad_scaled_device": (_c_int, [_c_i64] * 5 + [_vp] * 3 + [_c_i64] +
                                                    [_vp] * 10),
+        "dglhip_typed_linear_ok": (_c_int, [_c_i64] * 2),
+        "dglhip_typed_linear_msg_device": (_c_int, [_c_i64] * 4 + [_vp] * 8 + [_c_int] +
+                                           [_vp] * 2),
+        "dglhip_typed_linear_wgrad_device": (_c_int, [_c_i64] * 4 + [_vp] * 3 + [_c_i64] +
+                                             [_vp] * 10),
         "dglhip_gsddmm_attention_device": (_c_int, [_c_i64, _c_i64, _vp, _vp, _vp, _vp, _vp,
                                                     ctypes.c_float, ctypes.c_float,
                                                     ctypes.c_float, _c_int, _vp, _vp]),

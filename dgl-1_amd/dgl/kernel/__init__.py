@@ -27,7 +27,7 @@ One module per operator family, imported one way, policy -> plan -> csr ->
 spmm -> {rgcn, gat, segment}: ``policy`` (constants, the schedule policy),
 ``plan`` (the views of the native launch plan), ``csr`` (CSR, SparseAdj and
 their builders), ``spmm`` (g-SpMM / g-SDDMM, call timing), ``rgcn``
-(gather_rows, DistMult, the typed-block operator), ``gat`` (edge attention,
+(gather_rows, DistMult, the typed-block and typed-linear operators), ``gat`` (edge attention,
 the fused GAT layer, the edge softmax, the fused dot-product attention), ``segment`` (the segment reduction). This file only
 re-exports them, so callers keep ``kernel.<name>``.
 
@@ -71,7 +71,7 @@ from .rgcn import (  # noqa: F401
     TYPED_CHUNK, gather_rows, set_typed_block_width, _position_groups_items,
     _position_groups, _DistMult, distmult_score, distmult_link_loss, set_validate_indices,
     _typed_items, set_typed_block_messages, _typed_msg_ok, _run_typed_msg, _RelationGroups,
-    _typed_scale_fused, typed_block_spmm)
+    _typed_scale_fused, typed_block_spmm, _typed_linear_ok, typed_linear_spmm)
 from .gat import (  # noqa: F401
     edge_attention, set_gat_backward, set_gat_variant, gat_dropout_scale, gat_dropout_mask,
     _GATAggregate, _gat_el_grad, gat_aggregate, gat_logits, _logits_source,
@@ -85,7 +85,8 @@ __all__ = ["CSR", "SparseAdj", "build_csr", "gspmm", "gsddmm_dot",
 # the settings rebound after import, by owner: never copied into this namespace
 _SETTINGS = {"_GAT_BLOCK_BYTES": plan, "_GAT_BLOCK_BYTES_NOGRAD": plan,
              "_GAT_BWD_BLOCK_BYTES": plan, "_EL_GRAD_BLOCK_BYTES": plan,
-             "_GAT_BWD": gat, "_VALIDATE_INDICES": rgcn, "_CALL_EVENTS": spmm}
+             "_GAT_BWD": gat, "_VALIDATE_INDICES": rgcn, "_TYPED_LINEAR_BYTES": rgcn,
+             "_CALL_EVENTS": spmm}
 
 
 def __getattr__(name):

@@ -1,5 +1,6 @@
-"""R-GCN's operators: gather_rows, the DistMult decoder and its loss, and
-the typed-edge block-diagonal g-SpMM (csrc/typed_block.hip)."""
+"""R-GCN's operators: gather_rows, the DistMult decoder and its loss, the
+typed-edge block-diagonal g-SpMM (csrc/typed_block.hip) and the typed-edge
+dense g-SpMM of the basis layer (csrc/typed_linear.hip)."""
 from __future__ import absolute_import
 
 import os
@@ -401,6 +402,14 @@ def _run_typed_msg(csr, slot_map, groups, pos_row, ufeat2, weight, slot_norm, nb
         R, g_rel.numel(), nb, si, so, ptr(groups.ptr), ptr(g_ptr), ptr(g_rel), ptr(pos_row),
         ptr(groups.slot), ptr(ufeat2), ptr(operand_scale), ptr(weight),
         1 if weight_transposed else 0, ptr(msg), stream))
+    return _typed_msg_sum(csr, slot_map, slot_norm, msg, Fo, out_scale)
+
+
+def _typed_msg_sum(csr, slot_map, slot_norm, msg, Fo, out_scale):
+    """Each row of ``csr`` = the slot-order sum of its message rows (row
+    ``slot_map[k]``, None: k, of ``msg`` for slot k, times ``slot_norm[k]``),
+    times ``out_scale[row]``: the second launch of the message paths."""
+    dev = msg.device
     items = csr._plans.get("typed_items")
     if items is None:
         items = csr._plans["typed_items"] = _typed_items(csr.indptr, csr.nnz)
@@ -410,7 +419,7 @@ def _run_typed_msg(csr, slot_map, groups, pos_row, ufeat2, weight, slot_norm, nb
     check_call(LIB.dglhip_typed_msg_sum_device(
         csr.num_rows, item_row.numel(), Fo, ptr(csr.indptr), ptr(item_ptr), ptr(item_row),
         csr.num_rows, None, ptr(slot_map), ptr(slot_norm), ptr(msg), ptr(out_scale), ptr(out),
-        ptr(part), stream))
+        ptr(part), _stream_of(dev)))
     return out
 
 
@@ -552,32 +561,154 @@ def typed_block_spmm(adj, ufeat, weight, etype, enorm=None, row_scale=None):
              applied inside the kernels when the message path runs (no
              elementwise pass either way, r06), else by that product
     """
-    dev = ufeat.device
-    adj = adj.to(dev)
     R, nb, si, so = weight.shape
     if ufeat.shape[1] != nb * si:
         raise DGLError("ufeat width %d != num_blocks * in_block %d" % (ufeat.shape[1], nb * si))
+    adj, etype, en, rs = _typed_args("typed_block_spmm", adj, ufeat.device, R, etype, enorm,
+                                     row_scale)
+    dev = ufeat.device
+    if rs is None:
+        return _TypedBlock.apply(adj, etype, R, _f32c(ufeat), _f32c(weight), en)
+    if _typed_scale_fused(dev, nb, si, so):
+        return _TypedBlock.apply(adj, etype, R, _f32c(ufeat), _f32c(weight), en, rs)
+    return _TypedBlock.apply(adj, etype, R, _f32c(ufeat), _f32c(weight), en) * rs.unsqueeze(1)
+
+
+def _typed_args(who, adj, dev, R, etype, enorm, row_scale):
+    """The typed operators' graph arguments on ``dev``, checked: (adj, etype
+    int64, enorm or None, row_scale or None). Relations out of range raise
+    IndexError: host ids always, device ids on request (set_validate_indices)."""
+    adj = adj.to(dev)
     etype = torch.as_tensor(etype)
     if etype.numel() and (etype.device.type == "cpu" or (
             _VALIDATE_INDICES and not (dev.type == "cuda" and
                                        torch.cuda.is_current_stream_capturing()))):
         lo, hi = torch.stack([etype.min(), etype.max()]).tolist()
         if lo < 0 or hi >= R:
-            raise IndexError("typed_block_spmm: relations span [%d, %d], out of range for %d "
-                             "relation weights" % (lo, hi, R))
+            raise IndexError("%s: relations span [%d, %d], out of range for %d "
+                             "relation weights" % (who, lo, hi, R))
     etype = etype.to(device=dev, dtype=torch.int64).contiguous().reshape(-1)
     en = None if enorm is None else _f32c(enorm.to(dev).reshape(-1).detach())
     # one relation (and norm) per edge id: the kernels gather them by edge id
     E = adj.fwd.nnz
     if etype.numel() != E or (en is not None and en.numel() != E):
-        raise DGLError("typed_block_spmm: %d edges but etype has %d and enorm %s entries"
-                       % (E, etype.numel(), "no" if en is None else en.numel()))
+        raise DGLError("%s: %d edges but etype has %d and enorm %s entries"
+                       % (who, E, etype.numel(), "no" if en is None else en.numel()))
     if row_scale is None:
-        return _TypedBlock.apply(adj, etype, R, _f32c(ufeat), _f32c(weight), en)
+        return adj, etype, en, None
     rs = _f32c(torch.as_tensor(row_scale).to(dev).reshape(-1).detach())
     if rs.numel() != adj.fwd.num_rows:
-        raise DGLError("typed_block_spmm: row_scale has %d entries for %d rows"
-                       % (rs.numel(), adj.fwd.num_rows))
-    if _typed_scale_fused(dev, nb, si, so):
-        return _TypedBlock.apply(adj, etype, R, _f32c(ufeat), _f32c(weight), en, rs)
-    return _TypedBlock.apply(adj, etype, R, _f32c(ufeat), _f32c(weight), en) * rs.unsqueeze(1)
+        raise DGLError("%s: row_scale has %d entries for %d rows"
+                       % (who, rs.numel(), adj.fwd.num_rows))
+    return adj, etype, en, rs
+
+
+# ---------------------------------------------------------------------------
+# Typed-edge dense g-SpMM (R-GCN basis layer) on the f32 MFMA
+# ---------------------------------------------------------------------------
+# Most bytes of transient buffers a typed_linear_spmm call may allocate on
+# the MFMA path (the nnz x max(Fi, Fo) message rows and the items x Fi x Fo
+# partials of dW, float32); a larger call takes typed_block_spmm's route.
+# Read at call time: rebind it here (kernel.rgcn._TYPED_LINEAR_BYTES = n).
+_TYPED_LINEAR_BYTES = 1 << 30
+
+
+def _typed_linear_ok(dev, nnz, num_rels, Fi, Fo):
+    """typed_linear_spmm runs its MFMA kernels: on a device, widths inside
+    dglhip_typed_linear_ok, transient buffers under _TYPED_LINEAR_BYTES."""
+    if dev.type != "cuda" or LIB.dglhip_typed_linear_ok(Fi, Fo) != 1:
+        return False
+    items = max(num_rels, 1) + -(-nnz // TYPED_CHUNK)
+    return 4 * (nnz * max(Fi, Fo) + items * Fi * Fo) <= _TYPED_LINEAR_BYTES
+
+
+def _run_typed_linear(csr, slot_map, groups, pos_row, ufeat2, weight, slot_norm, Fi, Fo,
+                      operand_scale=None, out_scale=None, weight_transposed=False):
+    """_run_typed_msg with a dense Fi x Fo weight per relation: the messages
+    by the MFMA kernel (csrc/typed_linear.hip), then the same slot-order sum."""
+    dev = ufeat2.device
+    msg = torch.empty(max(csr.nnz, 1), Fo, dtype=torch.float32, device=dev)
+    g_ptr, g_rel = groups.items
+    check_call(LIB.dglhip_typed_linear_msg_device(
+        groups.ptr.numel() - 1, g_rel.numel(), Fi, Fo, ptr(groups.ptr), ptr(g_ptr), ptr(g_rel),
+        ptr(pos_row), ptr(groups.slot), ptr(ufeat2), ptr(operand_scale), ptr(weight),
+        1 if weight_transposed else 0, ptr(msg), _stream_of(dev)))
+    return _typed_msg_sum(csr, slot_map, slot_norm, msg, Fo, out_scale)
+
+
+class _TypedLinear(torch.autograd.Function):
+    """typed_linear_spmm on a device (the caller checked _typed_linear_ok)."""
+
+    @staticmethod
+    def forward(ctx, adj, etype, ufeat, weight, enorm, row_scale):
+        R, Fi, Fo = weight.shape
+        g = _relation_groups(adj, etype, R)
+        nrm = None if enorm is None else enorm.index_select(0, adj.fwd.eid)
+        out = _run_typed_linear(adj.fwd, None, g, g.src, ufeat, weight, nrm, Fi, Fo,
+                                out_scale=row_scale)
+        ctx.adj = adj
+        ctx.save_for_backward(etype, ufeat, weight, enorm, row_scale)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        etype, ufeat, weight, enorm, row_scale = ctx.saved_tensors
+        adj = ctx.adj
+        R, Fi, Fo = weight.shape
+        dout = _f32c(dout)
+        g = _relation_groups(adj, etype, R)
+        du = dw = None
+        if ctx.needs_input_grad[2]:
+            # messages dout[dst] Wt[r] at the forward slots (the weight read
+            # transposed in the kernel), summed along the transposed CSR
+            nrm = None if enorm is None else enorm.index_select(0, adj.bwd.eid)
+            du = _run_typed_linear(adj.bwd, _fwd_slot_of_bwd(adj), g, g.dst, dout, weight, nrm,
+                                   Fo, Fi, operand_scale=row_scale, weight_transposed=True)
+        if ctx.needs_input_grad[3]:
+            if adj.fwd.nnz == 0:
+                return None, None, du, torch.zeros_like(weight), None, None
+            nrm = None if enorm is None else enorm.index_select(
+                0, adj.fwd.eid.index_select(0, g.slot))
+            item_ptr, item_rel = g.items
+            dw = torch.empty_like(weight)
+            part = torch.empty(item_rel.numel(), Fi * Fo, dtype=torch.float32, device=dout.device)
+            check_call(LIB.dglhip_typed_linear_wgrad_device(
+                R, item_rel.numel(), Fi, Fo, ptr(g.ptr), ptr(item_ptr), ptr(item_rel), R, None,
+                ptr(g.src), ptr(g.dst), ptr(nrm), ptr(ufeat), ptr(dout), ptr(row_scale), ptr(dw),
+                ptr(part), _stream_of(dout.device)))
+        return None, None, du, dw, None, None
+
+
+def typed_linear_spmm(adj, ufeat, weight, etype, enorm=None, row_scale=None):
+    """R-GCN message passing with a dense weight per relation (the basis
+    layer, examples/pytorch/rgcn/layers.py:94-98):
+    out[v] = row_scale[v] * sum_{e=(u->v)} enorm[e] * (ufeat[u] @ weight[etype[e]]).
+
+    adj    : SparseAdj (rows = destinations) on the features' device
+    ufeat  : (num_src, Fi) float32 (autograd)
+    weight : (num_rels, Fi, Fo) float32 (autograd)
+    etype, enorm, row_scale : as typed_block_spmm takes them (ids checked the
+             same way; neither scale is differentiated)
+
+    On a ROCm device, for 1 <= Fi, Fo <= 256 (dglhip_typed_linear_ok), the
+    relation-major items run as grouped GEMMs on the f32 matrix instruction
+    (csrc/typed_linear.hip): messages at the forward slots, the slot-order
+    sum, dH by the same kernel with the weight read transposed, dW as a TN
+    product per item with the partials combined in item order. Deterministic
+    (no atomics: the same inputs give the same bits). Everything else — CPU
+    tensors, other widths, a call whose message rows and dW partials would
+    exceed ``_TYPED_LINEAR_BYTES`` — is
+    ``typed_block_spmm(adj, ufeat, weight.view(R, 1, Fi, Fo), ...)``. The two
+    routes agree to float32 rounding, not bit for bit: the matrix
+    instruction associates each element's sum over Fi (and dW's over the
+    positions) differently from the scalar chains, on the device and the host.
+    """
+    if weight.dim() != 3 or ufeat.dim() != 2 or ufeat.shape[1] != weight.shape[1]:
+        raise DGLError("typed_linear_spmm: ufeat %s does not match weight %s (num_rels, Fi, Fo)"
+                       % (tuple(ufeat.shape), tuple(weight.shape)))
+    R, Fi, Fo = weight.shape
+    dev = ufeat.device
+    if not _typed_linear_ok(dev, adj.fwd.nnz, R, Fi, Fo):
+        return typed_block_spmm(adj, ufeat, weight.reshape(R, 1, Fi, Fo), etype, enorm, row_scale)
+    adj, etype, en, rs = _typed_args("typed_linear_spmm", adj, dev, R, etype, enorm, row_scale)
+    return _TypedLinear.apply(adj, etype, _f32c(ufeat), _f32c(weight), en, rs)

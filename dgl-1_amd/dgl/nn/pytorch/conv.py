@@ -12,7 +12,9 @@ the later-DGL module names and arguments) on top of:
 * DotGatConv   : scaled dot-product attention over the in-edges in one kernel
                  (transformer/modules/models.py:79-86, kernel.dot_attention)
 * SAGEConv     : update_all(copy_src, mean) -> g-SpMM mean
-* RelGraphConv : typed-edge block-diagonal g-SpMM (rgcn/layers.py:121-132)
+* RelGraphConv : typed-edge block-diagonal g-SpMM (rgcn/layers.py:121-132), or
+                 with regularizer="basis" the dense per-relation weights of
+                 the basis layer on the f32 MFMA (rgcn/layers.py:52-100)
 """
 import math
 
@@ -150,30 +152,104 @@ class SAGEConv(nn.Module):
 
 
 class RelGraphConv(nn.Module):
-    """R-GCN layer with block-diagonal relation weights (num_bases blocks):
-    h' = act(norm * sum_{e=(u->v)} blockdiag(W[etype_e]) h_u + h W_loop + b)."""
+    """R-GCN layer, h' = act(norm * sum_{e=(u->v)} enorm_e W[etype_e] h_u + h W_loop + b).
+
+    regularizer="bdd" (the default): block-diagonal relation weights of
+    num_bases blocks, ``weight`` (num_rels, num_bases, in/num_bases,
+    out/num_bases), through kernel.typed_block_spmm.
+
+    regularizer="basis" (the reference's RGCNBasisLayer, rgcn/layers.py:
+    52-100): every relation a dense in_feat x out_feat weight composed from
+    ``weight`` (num_bases, in_feat, out_feat) by ``w_comp`` (num_rels,
+    num_bases; present only when num_bases < num_rels, and a num_bases <= 0 or
+    > num_rels means num_rels), through kernel.typed_linear_spmm. With
+    ``feat`` an int64 tensor of node ids (the featureless input layer) the
+    message is the row W[etype_e, feat[u], :]: one g-SpMM over the table
+    W.view(num_rels * in_feat, out_feat), no per-edge product."""
 
     def __init__(self, in_feat, out_feat, num_rels, num_bases, bias=True, activation=None,
-                 self_loop=True, dropout=0.0):
+                 self_loop=True, dropout=0.0, regularizer="bdd"):
         super(RelGraphConv, self).__init__()
-        if in_feat % num_bases or out_feat % num_bases:
-            raise DGLError("in/out features must be divisible by num_bases")
-        self.weight = nn.Parameter(torch.Tensor(num_rels, num_bases, in_feat // num_bases,
-                                                out_feat // num_bases))
-        nn.init.xavier_uniform_(self.weight, gain=nn.init.calculate_gain("relu"))
+        if regularizer not in ("bdd", "basis"):
+            raise DGLError("regularizer must be 'bdd' or 'basis', got %r" % (regularizer,))
+        self.regularizer = regularizer
+        self.in_feat, self.out_feat, self.num_rels = in_feat, out_feat, num_rels
+        gain = nn.init.calculate_gain("relu")
+        if regularizer == "basis":
+            if num_bases <= 0 or num_bases > num_rels:
+                num_bases = num_rels
+            self.weight = nn.Parameter(torch.Tensor(num_bases, in_feat, out_feat))
+            nn.init.xavier_uniform_(self.weight, gain=gain)
+            if num_bases < num_rels:
+                self.w_comp = nn.Parameter(torch.Tensor(num_rels, num_bases))
+                nn.init.xavier_uniform_(self.w_comp, gain=gain)
+            else:
+                self.w_comp = None
+        else:
+            if in_feat % num_bases or out_feat % num_bases:
+                raise DGLError("in/out features must be divisible by num_bases")
+            self.weight = nn.Parameter(torch.Tensor(num_rels, num_bases, in_feat // num_bases,
+                                                    out_feat // num_bases))
+            nn.init.xavier_uniform_(self.weight, gain=gain)
+        self.num_bases = num_bases
         self.loop_weight = nn.Parameter(torch.Tensor(in_feat, out_feat)) if self_loop else None
         if self_loop:
-            nn.init.xavier_uniform_(self.loop_weight, gain=nn.init.calculate_gain("relu"))
+            nn.init.xavier_uniform_(self.loop_weight, gain=gain)
         self.bias = nn.Parameter(torch.zeros(out_feat)) if bias else None
         self.activation = activation
         self.dropout = nn.Dropout(dropout) if dropout else None
 
-    def forward(self, g, feat, etype, norm=None):
-        rst = kernel.typed_block_spmm(g.sparse_adjacency(feat.device), feat, self.weight, etype)
-        if norm is not None:
-            rst = rst * norm.reshape(-1, 1)
+    def relation_weights(self):
+        """(num_rels, in_feat, out_feat): the basis layer's dense weights,
+        composed by torch so that autograd carries dW to weight and w_comp."""
+        if self.w_comp is None:
+            return self.weight
+        return (self.w_comp @ self.weight.view(self.num_bases, -1)).view(
+            self.num_rels, self.in_feat, self.out_feat)
+
+    def _table_adj(self, adj, ids, etype):
+        """The featureless layer's adjacency, rows = destinations and column
+        of edge e = etype[e] * in_feat + ids[src_e] (a row of the table
+        W.view(num_rels * in_feat, out_feat)); cached on ``adj`` for these
+        etype and ids tensors at their versions, as the relation grouping is."""
+        key = (etype.data_ptr(), etype.numel(), etype._version, ids.data_ptr(), ids.numel(),
+               ids._version, self.in_feat)
+        hit = getattr(adj, "_rel_table", None)
+        if hit is None or hit[0] != key:
+            dst, src = kernel.coo_of(adj.fwd)
+            col = etype * self.in_feat + ids.index_select(0, src)
+            table = kernel.from_coo(adj.fwd.num_rows, self.num_rels * self.in_feat, dst, col,
+                                    kernel.ORDER_EID, ids.device)
+            # (the keyed tensors are held: their memory is not reused meanwhile)
+            hit = adj._rel_table = (key, table, etype, ids)
+        return hit[1]
+
+    def forward(self, g, feat, etype, norm=None, enorm=None):
+        adj = g.sparse_adjacency(feat.device)
+        featureless = feat.dtype == torch.int64
+        if self.regularizer == "bdd":
+            rst = kernel.typed_block_spmm(adj, feat, self.weight, etype, enorm)
+            if norm is not None:
+                rst = rst * norm.reshape(-1, 1)
+        elif featureless:
+            et = torch.as_tensor(etype).to(device=feat.device, dtype=torch.int64).reshape(-1)
+            # (ids out of the table's range are refused where the adjacency over
+            # them is built, once per etype and ids: from_coo checks its columns)
+            table =self.relation_weights().reshape(self.num_rels * self.in_feat, self.out_feat)
+            tadj = self._table_adj(adj.to(feat.device), feat.reshape(-1), et)
+            if enorm is None:
+                rst = kernel.gspmm(tadj, kernel.MSG_COPY_U, kernel.RED_SUM, table)
+            else:
+                rst = kernel.gspmm(tadj, kernel.MSG_U_MUL_E, kernel.RED_SUM, table,
+                                   enorm.detach().reshape(-1, 1))
+            if norm is not None:
+                rst = rst * norm.reshape(-1, 1)
+        else:
+            rst = kernel.typed_linear_spmm(adj, feat, self.relation_weights(), etype, enorm,
+                                           row_scale=None if norm is None else norm.reshape(-1))
         if self.loop_weight is not None:
-            loop = feat @ self.loop_weight
+            loop = self.loop_weight.index_select(0, feat.reshape(-1)) if featureless \
+                else feat @ self.loop_weight
             rst = rst + (self.dropout(loop) if self.dropout is not None else loop)
         if self.bias is not None:
             rst = rst + self.bias

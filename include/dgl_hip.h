@@ -1560,6 +1560,43 @@ int dglhip_typed_block_wgrad_scaled_device(int64_t num_rels, int64_t num_items,
                                            const float* dout, const float* dout_scale,
                                            float* dweight, float* partial, void* stream);
 
+/* Typed-edge dense g-SpMM (R-GCN's basis layer: a full in_feat x out_feat
+ * weight per relation, float32[R, in_feat, out_feat]) on the f32 MFMA
+ * (csrc/typed_linear.hip). The message and weight-gradient entries of the
+ * block-diagonal operator above with one block, as grouped GEMMs over the
+ * relation-major items (64 positions of one relation per workgroup); the
+ * sum by destination is dglhip_typed_msg_sum_device, unchanged:
+ *   messages: msg[pos_slot[p] * out_feat + j] = sum_i ufeat[pos_row[p], i] *
+ *     (operand_scale[pos_row[p]], NULL = 1) * weight[r, i, j]
+ *     (weight_transposed = 1: weight is (R, out_feat, in_feat), read as its
+ *     transpose — the input gradient without a transposed copy);
+ *   weight gradient: dweight[r, i, j] = sum over the positions k of relation
+ *     r of rel_norm[k] * ufeat[rel_src[k], i] * dout[rel_dst[k], j] *
+ *     (dout_scale[rel_dst[k]], NULL = 1); items, heavy_rel and partial
+ *     (num_items x in_feat*out_feat floats) as dglhip_typed_block_wgrad_device.
+ * Each element is the MFMA's f32 fma chain over i (over k), an ordinary
+ * GEMM's association: deterministic, no atomics, but not the bits of the
+ * scalar entries above. dglhip_typed_linear_ok: 1 for the widths the kernels
+ * take, 1 <= in_feat, out_feat <= 256 (accumulator registers and the LDS
+ * weight tile, typed_linear.hip); the entries reject the rest. NULL
+ * per-position arrays declare that there are no positions, as above. */
+int dglhip_typed_linear_ok(int64_t in_feat, int64_t out_feat);
+int dglhip_typed_linear_msg_device(int64_t num_rels, int64_t num_items, int64_t in_feat,
+                                   int64_t out_feat, const int64_t* rel_ptr,
+                                   const int64_t* item_ptr, const int32_t* item_rel,
+                                   const int32_t* pos_row, const int64_t* pos_slot,
+                                   const float* ufeat, const float* operand_scale,
+                                   const float* weight, int weight_transposed, float* msg,
+                                   void* stream);
+int dglhip_typed_linear_wgrad_device(int64_t num_rels, int64_t num_items, int64_t in_feat,
+                                     int64_t out_feat, const int64_t* rel_ptr,
+                                     const int64_t* item_ptr, const int32_t* item_rel,
+                                     int64_t num_heavy, const int32_t* heavy_rel,
+                                     const int32_t* rel_src, const int32_t* rel_dst,
+                                     const float* rel_norm, const float* ufeat,
+                                     const float* dout, const float* dout_scale,
+                                     float* dweight, float* partial, void* stream);
+
 /* The typed-block entries' item list from a CSR-like ptr[num_rows+1]: item_ptr
  * [num_rows+1] (row r has max(1, ceil(deg / DGLHIP_TYPED_CHUNK)) items) and
  * item_row[bound] (each item's row; entries past the last item = num_rows),
