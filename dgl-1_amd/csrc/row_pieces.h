@@ -1,5 +1,5 @@
 // Long rows cut into pieces, shared by the kernels that walk a CSR row by row
-// (edge_softmax.hip, dot_attention.hip). A row of more than `chunk` slots is
+// (edge_softmax.hip, dot_attention.hip, gatv2_attention.hip). A row of more than `chunk` slots is
 // cut where it crosses the multiples of the chunk: block g is slots
 // [g chunk, (g + 1) chunk), and it meets at most two long rows, the one that
 // holds its first slot (item 2 g) and one that starts inside it (item

@@ -249,6 +249,15 @@ def _load():
                                       [_vp, _vp, _c_int]),
         "dglhip_dot_attention_bwd_host": (_c_int, [_c_i64] * 5 + [_vp] * 10 + [_c_float] * 3 +
                                           [_vp] * 4 + [_c_int]),
+        "dglhip_gatv2_attention_workspace_bytes": (_c_i64, [_c_i64] * 6 + [_c_int]),
+        "dglhip_gatv2_attention_device": (_c_int, [_c_i64] * 5 + [_vp] * 6 + [_c_float] +
+                                          [_vp, _vp, _c_i64, _vp, _vp]),
+        "dglhip_gatv2_attention_bwd_device": (_c_int, [_c_i64] * 5 + [_vp] * 12 + [_c_float] +
+                                              [_vp] * 4 + [_c_i64, _c_i64, _vp, _vp]),
+        "dglhip_gatv2_attention_host": (_c_int, [_c_i64] * 5 + [_vp] * 5 + [_c_float] +
+                                        [_vp, _vp, _c_int]),
+        "dglhip_gatv2_attention_bwd_host": (_c_int, [_c_i64] * 5 + [_vp] * 10 + [_c_float] +
+                                            [_vp] * 4 + [_c_int]),
         "dglhip_induced_subgraph_workspace_bytes": (_c_i64, [_c_i64, _c_i64, _c_i64]),
         "dglhip_induced_subgraph_count_device": (_c_int, [_c_i64, _c_i64, _c_i64, _vp, _vp, _vp,
                                                           _vp, _c_i64, _vp, _vp]),

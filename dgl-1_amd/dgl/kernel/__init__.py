@@ -76,7 +76,8 @@ from .gat import (  # noqa: F401
     edge_attention, set_gat_backward, set_gat_variant, gat_dropout_scale, gat_dropout_mask,
     _GATAggregate, _gat_el_grad, gat_aggregate, gat_logits, _logits_source,
     EDGE_SOFTMAX_CHUNK, edge_softmax, segment_softmax,
-    DOT_ATTENTION_CHUNK, DOT_ATTENTION_BATCH, dot_attention)
+    DOT_ATTENTION_CHUNK, DOT_ATTENTION_BATCH, dot_attention,
+    GATV2_CHUNK, GATV2_BATCH, GATV2_BATCH_DFD, GATV2_BATCH_DFS, gatv2_attention)
 from .segment import SEGMENT_CHUNK, SegmentOffsets, segment_reduce  # noqa: F401
 
 __all__ = ["CSR", "SparseAdj", "build_csr", "gspmm", "gsddmm_dot",

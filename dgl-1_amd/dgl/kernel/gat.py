@@ -1,8 +1,9 @@
 """The edge-attention operators: GAT's per-edge attention, its fused
 aggregation layer with its backwards and its attention logits
 (csrc/gat_fused.hip), the softmax over a node's edges
-(csrc/edge_softmax.hip) and the fused scaled dot-product attention
-(csrc/dot_attention.hip)."""
+(csrc/edge_softmax.hip), the fused scaled dot-product attention
+(csrc/dot_attention.hip) and the fused GATv2 attention
+(csrc/gatv2_attention.hip)."""
 from __future__ import absolute_import
 
 import os
@@ -10,6 +11,7 @@ import weakref
 
 import numpy as np
 import torch
+import torch.nn.functional as F
 
 from .._ffi import LIB, check_call, ptr, stream_of as _stream_of
 from ..base import DGLError
@@ -790,3 +792,133 @@ def dot_attention(adj, q, k, v, scale=None, clamp=None):
         return _dot_attention_composed(adj, q, k, v, scale, clamp)
     lo, hi = (-float("inf"), float("inf")) if clamp is None else (float(clamp[0]), float(clamp[1]))
     return _DotAttention.apply(adj, scale, lo, hi, q, k, v)
+
+
+# ---------------------------------------------------------------------------
+# GATv2 attention over the in-edges, fused (csrc/gatv2_attention.hip)
+# ---------------------------------------------------------------------------
+GATV2_CHUNK = 1024  # DGLHIP_GATV2_CHUNK: a longer row is cut into pieces
+GATV2_BATCH = 16  # DGLHIP_GATV2_BATCH: the forward's slots per rescale of the running sums
+GATV2_BATCH_DFD = 8  # DGLHIP_GATV2_BATCH_DFD: slots per batch of the backward over the CSR
+GATV2_BATCH_DFS = 8  # DGLHIP_GATV2_BATCH_DFS: the same over the transposed CSR
+
+
+def _gatv2_workspace(adj, H, D, dev, backward):
+    fwd = adj.fwd
+    nbytes = LIB.dglhip_gatv2_attention_workspace_bytes(
+        fwd.num_rows, fwd.nnz, H, D, fwd.max_degree, adj.bwd.max_degree if backward else 0,
+        1 if backward else 0)
+    return _workspace(nbytes, dev) if nbytes else None
+
+
+class _GATv2Attention(torch.autograd.Function):
+    """out = softmax over each destination's in-edges of <attn, lrelu(fs[u] +
+    fd[r])> times fs[u], in one pass with one gathered row per edge; the
+    backward recomputes the scores from fs, fd, attn and the saved lse: dfd and
+    dattn over the CSR, dfs over its transpose. Saves fs, fd, attn, out and
+    lse (rows, H): nothing per edge."""
+
+    @staticmethod
+    def forward(ctx, adj, slope, fs, fd, attn):
+        fwd = adj.fwd
+        R, H, D = fd.shape
+        dev = fd.device
+        out = torch.empty_like(fd)
+        lse = torch.empty(R, H, dtype=torch.float32, device=dev)
+        head = (R, fwd.num_cols, fwd.nnz, H, D, ptr(fwd.indptr), ptr(fwd.indices))
+        if dev.type == "cuda":
+            ws = _gatv2_workspace(adj, H, D, dev, False)
+            check_call(LIB.dglhip_gatv2_attention_device(*(head + (
+                ptr(fwd.row_order), ptr(fs), ptr(fd), ptr(attn), slope, ptr(out), ptr(lse),
+                fwd.max_degree, ptr(ws), _stream_of(dev)))))
+        else:
+            check_call(LIB.dglhip_gatv2_attention_host(*(head + (
+                ptr(fs), ptr(fd), ptr(attn), slope, ptr(out), ptr(lse), 0))))
+        ctx.adj, ctx.slope = adj, slope
+        ctx.save_for_backward(fs, fd, attn, out, lse)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        fs, fd, attn, out, lse = ctx.saved_tensors
+        fwd, bwd = ctx.adj.fwd, ctx.adj.bwd
+        R, H, D = fd.shape
+        dev = fd.device
+        dout = _f32c(dout)
+        if dout.data_ptr() % 16:
+            # a gradient that arrives as a view at an odd offset would narrow
+            # the accesses below what the forward's gate found for this D
+            dout = dout.clone()
+        delta = torch.empty_like(lse)
+        dfs, dfd, dattn = torch.empty_like(fs), torch.empty_like(fd), torch.empty_like(attn)
+        head = (R, fwd.num_cols, fwd.nnz, H, D, ptr(fwd.indptr), ptr(fwd.indices))
+        mid = (ptr(fs), ptr(fd), ptr(attn), ptr(out), ptr(lse), ptr(dout), ctx.slope,
+               ptr(delta), ptr(dfs), ptr(dfd), ptr(dattn))
+        if dev.type == "cuda":
+            ws = _gatv2_workspace(ctx.adj, H, D, dev, True)
+            check_call(LIB.dglhip_gatv2_attention_bwd_device(*(
+                head + (ptr(fwd.row_order), ptr(bwd.indptr), ptr(bwd.indices),
+                        ptr(bwd.row_order)) + mid +
+                (fwd.max_degree, bwd.max_degree, ptr(ws), _stream_of(dev)))))
+        else:
+            check_call(LIB.dglhip_gatv2_attention_bwd_host(*(
+                head + (ptr(bwd.indptr), ptr(bwd.indices)) + mid + (0,))))
+        return None, None, dfs, dfd, dattn
+
+
+def _gatv2_attention_composed(adj, fs, fd, attn, slope, attn_drop=0.0):
+    """The attention from the operators it fuses, every edge tensor in forward
+    slot order (an E x H x D intermediate): heads wider than the fused
+    kernels' lane map, and dropout on the attention."""
+    fwd = adj.fwd
+    z = fs.index_select(0, fwd.indices.long()) + fd.index_select(0, fwd.row_ids())
+    s = (F.leaky_relu(z, slope) * attn).sum(-1)
+    a = edge_softmax(adj, s, "dst", "slot")
+    if attn_drop > 0:
+        a = F.dropout(a, attn_drop)
+    return gspmm(adj, "u_mul_e", "sum", fs, a.unsqueeze(-1), edge_order="slot")
+
+
+def gatv2_attention(adj, fs, fd, attn, negative_slope=0.2, attn_drop=0.0):
+    """GATv2 attention (Brody et al., "How Attentive are Graph Attention
+    Networks?") over the edges of ``adj``: for every destination r, head h
+    and in-edge j from source u_j,
+
+        s_j = sum_d attn[h, d] * leaky_relu(fs[u_j, h, d] + fd[r, h, d], negative_slope)
+        out[r, h] = sum_j softmax_j(s) fs[u_j, h]
+
+    fs (num_cols, H, D), fd (num_rows, H, D), attn (H, D) or (1, H, D)
+    float32; returns (num_rows, H, D), differentiable in all three (the
+    leaky_relu's gradient at 0 is the slope, as torch's). A destination
+    without in-edges gets zeros and passes no gradient. One kernel forward
+    with one gathered source row per edge, two walks backward
+    (csrc/gatv2_attention.hip): no tensor of the size of the edge set is made
+    or kept, only out and a (num_rows, H) log-sum-exp. No atomics: the same
+    bits on every call, dattn included. Heads wider than 64 * V (V as
+    dot_attention's) and ``attn_drop`` > 0 (torch dropout on the attention:
+    pass it in training only) run as the composition torch indexing,
+    leaky_relu, edge_softmax, gspmm."""
+    for name, t in (("fs", fs), ("fd", fd)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 3:
+            raise DGLError("gatv2_attention: %s must be a (rows, heads, features) tensor" % name)
+    if fs.shape[1:] != fd.shape[1:] or not isinstance(attn, torch.Tensor) or \
+            attn.dim() not in (2, 3) or attn.numel() != fs.shape[1] * fs.shape[2] or \
+            attn.shape[-2:] != fs.shape[1:]:
+        raise DGLError("gatv2_attention: fs %s, fd %s and attn %s differ in heads or features"
+                       % (tuple(fs.shape), tuple(fd.shape),
+                          tuple(attn.shape) if isinstance(attn, torch.Tensor) else attn))
+    if not 0.0 <= float(attn_drop) < 1.0:
+        raise DGLError("attention dropout must be in [0, 1), got %r" % (attn_drop,))
+    dev = fd.device
+    adj = adj.to(dev)
+    if fd.shape[0] != adj.shape[0] or fs.shape[0] != adj.shape[1]:
+        raise DGLError("gatv2_attention: %d rows of fd and %d of fs for a %d x %d adjacency"
+                       % (fd.shape[0], fs.shape[0], adj.shape[0], adj.shape[1]))
+    H, D = fs.shape[1:]
+    fs, fd, attn = _f32c(fs), _f32c(fd), _f32c(attn.reshape(H, D))
+    if fd.numel() == 0 or adj.fwd.nnz == 0:
+        return torch.zeros_like(fd)
+    slope = float(negative_slope)
+    if attn_drop > 0 or D > 64 * _dot_attention_vec(D, (fs, fd, attn)):
+        return _gatv2_attention_composed(adj, fs, fd, attn, slope, float(attn_drop))
+    return _GATv2Attention.apply(adj, slope, fs, fd, attn)

@@ -9,6 +9,8 @@ the later-DGL module names and arguments) on top of:
 * GraphConv    : update_all(copy_src, sum) -> one g-SpMM (gcn_spmv.py:45-62)
 * GATConv      : attention, dropout, per-head weighted sum and copy_edge
                  normaliser in one kernel (gat/train.py:61-96, kernel.gat_aggregate)
+* GATv2Conv    : GATv2 attention over the in-edges in one kernel, one gathered
+                 row per edge (later DGL's GATv2Conv, kernel.gatv2_attention)
 * DotGatConv   : scaled dot-product attention over the in-edges in one kernel
                  (transformer/modules/models.py:79-86, kernel.dot_attention)
 * SAGEConv     : update_all(copy_src, mean) -> g-SpMM mean
@@ -27,7 +29,7 @@ from ... import kernel
 from ...base import DGLError
 from .linear import NodeLinear, sage_dense, bias_add
 
-__all__ = ["GraphConv", "GATConv", "DotGatConv", "SAGEConv", "RelGraphConv"]
+__all__ = ["GraphConv", "GATConv", "GATv2Conv", "DotGatConv", "SAGEConv", "RelGraphConv"]
 
 
 class GraphConv(nn.Module):
@@ -106,6 +108,52 @@ class GATConv(nn.Module):
             attn_drop=self.attn_drop.p if self.attn_drop is not None else 0.0,
             training=self.training)
         rst = ft_sum / z.clamp(min=1e-20)
+        if self.res_fc is not None:
+            rst = rst + self.res_fc(h).view(-1, self.num_heads, self.out_feats)
+        return self.activation(rst) if self.activation else rst
+
+
+class GATv2Conv(nn.Module):
+    """Multi-head GATv2 attention (Brody et al.): e = <attn, leaky_relu(W_src
+    h_u + W_dst h_v)>, softmax over v's in-edges, the sum of W_src h_u
+    weighted by it; returns (N, num_heads, out_feats). ``share_weights``: one
+    projection for both sides. The attention, its softmax and the sum run in
+    one kernel (kernel.gatv2_attention) unless dropout on the attention is
+    active (``attn_drop`` > 0 in training), which runs the composition."""
+
+    def __init__(self, in_feats, out_feats, num_heads, feat_drop=0., attn_drop=0.,
+                 negative_slope=0.2, residual=False, activation=None, bias=True,
+                 share_weights=False):
+        super(GATv2Conv, self).__init__()
+        self.num_heads, self.out_feats = num_heads, out_feats
+        self.fc_src = nn.Linear(in_feats, num_heads * out_feats, bias=bias)
+        self.fc_dst = self.fc_src if share_weights else \
+            nn.Linear(in_feats, num_heads * out_feats, bias=bias)
+        self.attn = nn.Parameter(torch.Tensor(1, num_heads, out_feats))
+        self.feat_drop = nn.Dropout(feat_drop) if feat_drop else None
+        self.attn_drop = float(attn_drop)
+        self.negative_slope = negative_slope
+        self.res_fc = None
+        if residual:
+            self.res_fc = nn.Identity() if in_feats == num_heads * out_feats else \
+                nn.Linear(in_feats, num_heads * out_feats, bias=bias)
+        self.activation = activation
+        gain = nn.init.calculate_gain("relu")
+        nn.init.xavier_normal_(self.fc_src.weight, gain=gain)
+        nn.init.xavier_normal_(self.fc_dst.weight, gain=gain)
+        nn.init.xavier_normal_(self.attn, gain=gain)
+        for fc in (self.fc_src, self.fc_dst):
+            if fc.bias is not None:
+                nn.init.zeros_(fc.bias)
+
+    def forward(self, g, feat):
+        h = self.feat_drop(feat) if self.feat_drop is not None else feat
+        fs = self.fc_src(h).view(-1, self.num_heads, self.out_feats)
+        fd = fs if self.fc_dst is self.fc_src else \
+            self.fc_dst(h).view(-1, self.num_heads, self.out_feats)
+        rst = kernel.gatv2_attention(g.sparse_adjacency(feat.device), fs, fd, self.attn,
+                                     self.negative_slope,
+                                     attn_drop=self.attn_drop if self.training else 0.0)
         if self.res_fc is not None:
             rst = rst + self.res_fc(h).view(-1, self.num_heads, self.out_feats)
         return self.activation(rst) if self.activation else rst

@@ -1,12 +1,13 @@
 """Softmax over the edges of each node (the ``edge_softmax`` later releases of
 the reference added to ``dgl.nn.pytorch``): one HIP kernel forward and one
 backward (``kernel.edge_softmax``, csrc/edge_softmax.hip), and the fused
-scaled dot-product attention over them (``kernel.dot_attention``)."""
+attentions over them: scaled dot-product (``kernel.dot_attention``) and GATv2
+(``kernel.gatv2_attention``)."""
 from __future__ import absolute_import
 
 from ... import kernel
 
-__all__ = ["edge_softmax", "dot_attention"]
+__all__ = ["edge_softmax", "dot_attention", "gatv2_attention"]
 
 
 def edge_softmax(graph, logits, norm_by="dst"):
@@ -40,3 +41,18 @@ def dot_attention(graph, q, k, v, scale=None, clamp=None):
     ...                                             # edge_softmax, update_all
     """
     return kernel.dot_attention(graph.sparse_adjacency(q.device), q, k, v, scale, clamp)
+
+
+def gatv2_attention(graph, fs, fd, attn, negative_slope=0.2):
+    """GATv2 attention over the edges of ``graph``: every node attends over
+    its in-edges, ``out[n, h] = sum_j softmax_j(<attn[h], leaky_relu(fs[u_j, h]
+    + fd[n, h])>) fs[u_j, h]``. ``fs`` and ``fd`` are ``(N, H, D)`` float32
+    node tensors (the source and destination projections), ``attn`` is ``(H,
+    D)`` or ``(1, H, D)``; returns ``(N, H, D)``, differentiable in all three,
+    a node without in-edges gets zeros. One fused HIP kernel forward with one
+    gathered row per edge, two walks backward (``kernel.gatv2_attention``,
+    csrc/gatv2_attention.hip): no per-edge tensor is made.
+
+    >>> out = gatv2_attention(g, fc_src(x).view(-1, H, D), fc_dst(x).view(-1, H, D), attn)
+    """
+    return kernel.gatv2_attention(graph.sparse_adjacency(fd.device), fs, fd, attn, negative_slope)

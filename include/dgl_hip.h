@@ -663,6 +663,82 @@ int dglhip_dot_attention_bwd_host(int64_t num_rows, int64_t num_cols, int64_t nn
                                   float* delta, float* dq, float* dk, float* dv, int num_threads);
 
 /* ------------------------------------------------------------------------ */
+/* GATv2 attention over a graph's in-edges, fused                            */
+/* (csrc/gatv2_attention.hip, csrc/gatv2_attention_host.cc). The CSR is the  */
+/* dot-product attention's: rows the num_rows destinations, columns the      */
+/* num_cols sources. fs: float32 [num_cols, H, D]; fd: [num_rows, H, D];     */
+/* attn: [H, D], all packed. Per row r, head h and slot j (source u_j), in   */
+/* float32:                                                                  */
+/*   z_j[d] = fs[u_j,h,d] + fd[r,h,d],                                       */
+/*   s_j = sum_d attn[h,d] lrelu(z_j[d]), lrelu(z) = z > 0 ? z : slope z,    */
+/*   a_j = expf(s_j - m) / l, m = max_j s_j, l = sum_j expf(s_j - m),        */
+/*   out[r,h,:] = sum_j a_j fs[u_j,h,:], lse[r,h] = m + logf(l).             */
+/* A row without slots stores zeros in out and 0 in lse.                     */
+/* Backward, from dout [num_rows, H, D] and the forward's out and lse, with  */
+/* delta[r,h] = <dout[r,h,:], out[r,h,:]> (written, [num_rows, H]),          */
+/* a_j = expf(s_j - lse), dp_j = <dout[r,h,:], fs[u_j,h,:]>,                 */
+/* ds_j = a_j (dp_j - delta) and g'(z) = z > 0 ? 1 : slope:                  */
+/*   dfd[r,h,d] = attn[h,d] sum_j ds_j g'(z_j[d]),                           */
+/*   dfs[u,h,d] = sum (a_j dout[r,h,d] + ds_j attn[h,d] g'(z_j[d])) over the */
+/*   transposed CSR (t_*: rows = sources, indices = destinations),           */
+/*   dattn[h,d] = sum over all slots of ds_j lrelu(z_j[d]).                  */
+/* Nothing of nnz entries is stored; no atomics, every output element has    */
+/* one writer (dattn: per-row partials in the workspace, added in a fixed    */
+/* order), the same bits on every call. The device forms serve head_dim <=   */
+/* 64 V as the dot-product attention's do. A row (a source, in the           */
+/* transposed walk) of more than DGLHIP_GATV2_CHUNK slots is cut into pieces */
+/* combined through `workspace`. Slots run in batches of DGLHIP_GATV2_BATCH  */
+/* (forward, one rescale of the running sums per batch), _BATCH_DFD (the     */
+/* backward's walk over the CSR) and _BATCH_DFS (over the transposed CSR).   */
+/* ------------------------------------------------------------------------ */
+#define DGLHIP_GATV2_CHUNK 1024
+#define DGLHIP_GATV2_BATCH 16
+#define DGLHIP_GATV2_BATCH_DFD 8
+#define DGLHIP_GATV2_BATCH_DFS 8
+/* Bytes of the device forms' workspace: the forward's (backward 0; 0 bytes
+ * when max_row_len is known, not -1, and at most the chunk) or the
+ * backward's (backward 1, never 0: the dattn partials, (num_rows + 2 blocks
+ * of the chunk when rows are cut + 1024) H D floats, beside the pieces of
+ * either CSR). */
+int64_t dglhip_gatv2_attention_workspace_bytes(int64_t num_rows, int64_t nnz, int64_t num_heads,
+                                               int64_t head_dim, int64_t max_row_len,
+                                               int64_t max_col_len, int backward);
+/* Device forms: as the dot-product attention's (device pointers, row_order
+ * only schedules, launch sizes from the sizes alone, indptr entries and
+ * column ids clamped, never followed beyond). */
+int dglhip_gatv2_attention_device(int64_t num_rows, int64_t num_cols, int64_t nnz,
+                                  int64_t num_heads, int64_t head_dim, const int64_t* indptr,
+                                  const int32_t* indices, const int32_t* row_order,
+                                  const float* fs, const float* fd, const float* attn,
+                                  float negative_slope, float* out, float* lse,
+                                  int64_t max_row_len, void* workspace, void* stream);
+int dglhip_gatv2_attention_bwd_device(int64_t num_rows, int64_t num_cols, int64_t nnz,
+                                      int64_t num_heads, int64_t head_dim, const int64_t* indptr,
+                                      const int32_t* indices, const int32_t* row_order,
+                                      const int64_t* t_indptr, const int32_t* t_indices,
+                                      const int32_t* t_row_order, const float* fs,
+                                      const float* fd, const float* attn, const float* out,
+                                      const float* lse, const float* dout, float negative_slope,
+                                      float* delta, float* dfs, float* dfd, float* dattn,
+                                      int64_t max_row_len, int64_t max_col_len, void* workspace,
+                                      void* stream);
+/* Host forms (thread pool), one sequential pass per row in slot order, any
+ * head_dim; dattn is summed over fixed ranges of rows, then over the ranges:
+ * the same bits at every thread count. A malformed CSR returns -1. */
+int dglhip_gatv2_attention_host(int64_t num_rows, int64_t num_cols, int64_t nnz,
+                                int64_t num_heads, int64_t head_dim, const int64_t* indptr,
+                                const int32_t* indices, const float* fs, const float* fd,
+                                const float* attn, float negative_slope, float* out, float* lse,
+                                int num_threads);
+int dglhip_gatv2_attention_bwd_host(int64_t num_rows, int64_t num_cols, int64_t nnz,
+                                    int64_t num_heads, int64_t head_dim, const int64_t* indptr,
+                                    const int32_t* indices, const int64_t* t_indptr,
+                                    const int32_t* t_indices, const float* fs, const float* fd,
+                                    const float* attn, const float* out, const float* lse,
+                                    const float* dout, float negative_slope, float* delta,
+                                    float* dfs, float* dfd, float* dattn, int num_threads);
+
+/* ------------------------------------------------------------------------ */
 /* Node-induced subgraph on the device (csrc/induced_subgraph.hip): the      */
 /* reference's Graph::VertexSubgraph (src/graph/graph.cc:441-469) over a     */
 /* source-major CSR that is already on the device: indptr int64[num_nodes +  */
