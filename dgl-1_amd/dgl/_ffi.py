@@ -233,6 +233,14 @@ def _load():
                                              [_c_i64] + [_vp] * 7),
         "dglhip_segment_reduce_bwd_host": (_c_int, [_c_int, _c_i64, _c_i64, _c_i64] + [_vp] * 3 +
                                            [_c_i64] + [_vp] * 6 + [_c_int]),
+        "dglhip_segment_topk_workspace_bytes": (_c_i64, [_c_i64] * 4 + [_c_int, _c_i64]),
+        "dglhip_segment_topk_device": (_c_int, [_c_i64] * 4 + [_c_int, _c_i64, _vp, _vp, _c_i64,
+                                                _vp, _vp, _c_i64, _vp, _vp]),
+        "dglhip_segment_topk_host": (_c_int, [_c_i64] * 4 + [_c_int, _c_i64, _vp, _vp, _c_i64,
+                                              _vp, _vp, _c_int]),
+        "dglhip_segment_topk_bwd_device": (_c_int, [_c_i64] * 4 + [_c_int, _c_i64] + [_vp] * 5),
+        "dglhip_segment_topk_bwd_host": (_c_int, [_c_i64] * 4 + [_c_int, _c_i64] + [_vp] * 4 +
+                                         [_c_int]),
         "dglhip_edge_softmax_workspace_bytes": (_c_i64, [_c_i64, _c_i64, _c_i64]),
         "dglhip_edge_softmax_device": (_c_int, [_c_i64, _c_i64, _c_i64] + [_vp] * 5 +
                                        [_c_i64, _vp, _vp]),

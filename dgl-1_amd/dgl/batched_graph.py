@@ -12,6 +12,9 @@ readout here is one call of ``kernel.segment_reduce``: a batch's nodes (and
 edges) of one graph are consecutive rows, so the graphs are the segments.
 ``softmax_nodes`` / ``softmax_edges`` normalise a feature over each member
 graph the same way, on the edge-softmax kernel (``kernel.segment_softmax``).
+``topk_nodes`` / ``topk_edges`` select each graph's first ``k`` rows in sorted
+order on the segment top-k kernel (``kernel.segment_topk``), where the
+reference pads every graph to the longest one and calls ``torch.topk``.
 """
 from __future__ import absolute_import
 
@@ -26,7 +29,7 @@ from .frame import Frame
 from .graph import DGLGraph
 
 __all__ = ["BatchedDGLGraph", "batch", "unbatch", "split", "sum_nodes", "sum_edges",
-           "mean_nodes", "mean_edges", "max_nodes", "max_edges", "softmax_nodes", "softmax_edges"]
+           "mean_nodes", "mean_edges", "max_nodes", "max_edges", "softmax_nodes", "softmax_edges", "topk_nodes", "topk_edges"]
 
 
 def _items_and_fields(g, mode):
@@ -245,3 +248,38 @@ def softmax_nodes(graph, feat):
 def softmax_edges(graph, feat):
     """:func:`softmax_nodes` over edge fields."""
     return _softmax_readout(graph, "edges", feat)
+
+
+def _topk_segments(graph, typestr, num_rows):
+    if isinstance(graph, BatchedDGLGraph):
+        return graph._readout_segments(typestr)
+    # a plain graph is one segment and keeps a batch dimension of 1
+    return kernel.SegmentOffsets(sizes=[num_rows])
+
+
+def _topk_readout(graph, typestr, feat, k, descending, idx):
+    x = (graph.ndata if typestr == "nodes" else graph.edata)[feat]
+    return kernel.segment_topk(x, _topk_segments(graph, typestr, x.shape[0]), k, descending, idx)
+
+
+def topk_nodes(graph, feat, k, descending=True, idx=None):
+    """Per graph, the first ``k`` nodes of field ``feat`` in sorted order
+    (largest first unless ``descending=False``), as ``(values, indices)``.
+
+    ``idx=None`` ranks every feature position on its own: ``values`` and the
+    int64 ``indices`` are ``(batch_size, k, *fshape)``, ``indices[b, j, f]``
+    the node within graph ``b`` whose value is ``values[b, j, f]``. ``idx=c``
+    ranks whole rows by position ``c`` (negative counts from the end):
+    ``values (batch_size, k, *fshape)`` are the selected rows and ``indices
+    (batch_size, k)`` their nodes. A field with more than one feature
+    dimension is ranked as flattened rows, so ``idx`` is then a position of
+    the flattened row. A plain graph is a batch of one: the leading dimension
+    is 1. Ties go to the lower node id, NaN counts as the largest value, and a
+    graph of fewer than ``k`` nodes fills the remaining slots with zeros and
+    index -1 (``kernel.segment_topk``). Differentiable in the field."""
+    return _topk_readout(graph, "nodes", feat, k, descending, idx)
+
+
+def topk_edges(graph, feat, k, descending=True, idx=None):
+    """:func:`topk_nodes` over edge fields."""
+    return _topk_readout(graph, "edges", feat, k, descending, idx)

@@ -1,5 +1,5 @@
-"""The segment reduction: the readout of a batched graph
-(csrc/segment_reduce.hip)."""
+"""The segment reduction (csrc/segment_reduce.hip) and the segment top-k
+(csrc/segment_topk.hip): the readouts of a batched graph."""
 from __future__ import absolute_import
 
 import numpy as np
@@ -14,6 +14,7 @@ from .spmm import _f32c
 # Segment reduction: the readout of a batched graph (csrc/segment_reduce.hip)
 # ---------------------------------------------------------------------------
 SEGMENT_CHUNK = 1024  # DGLHIP_SEGMENT_CHUNK: rows per chain of the segment reduction
+TOPK_CHUNK = 2048  # DGLHIP_TOPK_CHUNK: rows one workgroup ranks in LDS, and the largest k
 
 
 class SegmentOffsets(object):
@@ -192,3 +193,108 @@ def segment_reduce(x, offsets, reduce, weight=None):
     if x.dim() == 2:
         return _SegmentReduce.apply(x, w, segs, red)
     return _SegmentReduce.apply(x.reshape(N, F), w, segs, red).view((B,) + fshape)
+
+
+# ---------------------------------------------------------------------------
+# Segment top-k: topk_nodes / topk_edges, SortPooling (csrc/segment_topk.hip)
+# ---------------------------------------------------------------------------
+class _SegmentTopk(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x2, segs, k, descending, sortby):
+        N, F = x2.shape
+        B = segs.num_segments
+        dev = x2.device
+        values = torch.empty(B, k, F, dtype=torch.float32, device=dev)
+        indices = torch.empty((B, k) if sortby >= 0 else (B, k, F), dtype=torch.int64,
+                              device=dev)
+        if N == 0:  # no rows (and no storage to point the library at): all padding
+            values.zero_()
+            indices.fill_(-1)
+        else:
+            off = segs.on(dev)
+            xv, ldx = _rows_view(x2.detach(), F)
+            if dev.type == "cuda":
+                nbytes = 0
+                if segs.max_rows < 0 or segs.max_rows > TOPK_CHUNK:
+                    nbytes = LIB.dglhip_segment_topk_workspace_bytes(B, N, F, k, descending,
+                                                                     sortby)
+                ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+                check_call(LIB.dglhip_segment_topk_device(
+                    B, N, F, k, descending, sortby, ptr(off), ptr(xv), ldx, ptr(values),
+                    ptr(indices), segs.max_rows, ptr(ws), _stream_of(dev)))
+            else:
+                check_call(LIB.dglhip_segment_topk_host(
+                    B, N, F, k, descending, sortby, ptr(off), ptr(xv), ldx, ptr(values),
+                    ptr(indices), 0))
+        ctx.segs, ctx.args = segs, (N, F, k, descending, sortby)
+        ctx.save_for_backward(indices)
+        ctx.mark_non_differentiable(indices)
+        return values, indices
+
+    @staticmethod
+    def backward(ctx, dy, _):
+        indices, = ctx.saved_tensors
+        N, F, k, descending, sortby = ctx.args
+        segs = ctx.segs
+        dev = indices.device
+        dy = _f32c(dy)
+        dx = torch.empty(N, F, dtype=torch.float32, device=dev)
+        fn = LIB.dglhip_segment_topk_bwd_device if dev.type == "cuda" \
+            else LIB.dglhip_segment_topk_bwd_host
+        check_call(fn(segs.num_segments, N, F, k, descending, sortby, ptr(segs.on(dev)), ptr(dy),
+                      ptr(indices), ptr(dx), _stream_of(dev) if dev.type == "cuda" else 0))
+        return dx, None, None, None, None
+
+
+def segment_topk(x, offsets, k, descending=True, sortby=None):
+    """The first ``k`` rows of every segment ``x[offsets[s] : offsets[s+1]]``
+    in sorted order, differentiable in ``x``.
+
+    ``x`` is ``(N, *fshape)`` float32 (any strides) with ``F`` elements per
+    row, ``offsets`` what :func:`segment_reduce` takes, ``1 <= k <=
+    TOPK_CHUNK``. ``sortby=None`` ranks every column on its own and returns
+    ``values (B, k, *fshape)`` and int64 ``indices (B, k, *fshape)``:
+    ``values[s, j, f]`` is the j-th element of column ``f`` of segment ``s``
+    and ``indices[s, j, f]`` its row within the segment. ``sortby=c`` (``-F <=
+    c < F``, a position of the flattened row) ranks whole rows by column ``c``
+    and returns the selected rows ``values (B, k, *fshape)`` and ``indices (B,
+    k)``.
+
+    The order is that of ``torch.sort(stable=True, descending=descending)`` on
+    the CPU: descending puts NaN first and then decreasing values, ascending
+    increasing values and NaN last; ``+0.0 == -0.0``, all NaNs are equal, and
+    among equal keys the lower row comes first. Values are moved, never
+    computed, so the output bits are the input bits. A segment of fewer than
+    ``k`` rows fills the remaining slots with ``+0.0`` and index ``-1``. Same
+    bits on the host and on the device, no atomics; ``k > TOPK_CHUNK`` is an
+    error, not another path."""
+    if not isinstance(x, torch.Tensor) or x.dim() < 1:
+        raise DGLError("segment_topk expects a tensor of rows")
+    if x.dtype != torch.float32:
+        raise DGLError("segment_topk ranks float32, got %s" % x.dtype)
+    k = int(k)
+    if k < 1 or k > TOPK_CHUNK:
+        raise DGLError("segment_topk serves 1 <= k <= TOPK_CHUNK = %d, got k = %d"
+                       % (TOPK_CHUNK, k))
+    segs = _segment_offsets(offsets)
+    N = x.shape[0]
+    fshape = tuple(x.shape[1:])
+    if segs.num_rows >= 0 and segs.num_rows != N:
+        raise DGLError("offsets end at %d, expected the %d rows" % (segs.num_rows, N))
+    B = segs.num_segments
+    F = 1
+    for d in fshape:
+        F *= d
+    col = -1
+    if sortby is not None:
+        col = int(sortby)
+        if col < -F or col >= F:
+            raise DGLError("sortby = %d is no column of rows of %d elements" % (col, F))
+        col %= F
+    if B == 0 or F == 0:
+        return (x.new_zeros((B, k) + fshape),
+                torch.full((B, k) + (fshape if col < 0 else ()), -1, dtype=torch.int64,
+                           device=x.device))
+    values, indices = _SegmentTopk.apply(x.reshape(N, F), segs, k, 1 if descending else 0, col)
+    values = values.view((B, k) + fshape)
+    return values, (indices if col >= 0 else indices.view((B, k) + fshape))

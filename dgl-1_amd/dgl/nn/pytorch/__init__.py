@@ -7,3 +7,4 @@ from .conv import DotGatConv, GATConv, GATv2Conv, GraphConv, RelGraphConv, SAGEC
 from .linear import NodeLinear, bias_add, dense_mm, node_epilogue, sage_dense  # noqa: F401
 from .loss import weighted_cross_entropy  # noqa: F401
 from .softmax import dot_attention, edge_softmax, gatv2_attention  # noqa: F401
+from .glob import SortPooling  # noqa: F401

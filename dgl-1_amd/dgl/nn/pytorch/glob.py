@@ -1,0 +1,36 @@
+"""Global pooling over the graphs of a batch (the ``glob`` module later
+releases of the reference added to ``dgl.nn.pytorch``)."""
+from __future__ import absolute_import
+
+import torch
+from torch import nn
+
+from ... import kernel
+from ...batched_graph import _topk_segments
+
+__all__ = ["SortPooling"]
+
+
+class SortPooling(nn.Module):
+    """The sort pooling of DGCNN (Zhang et al., "An End-to-End Deep Learning
+    Architecture for Graph Classification", AAAI 2018): every node's channels
+    are sorted ascending, then each graph keeps its ``k`` nodes with the
+    largest last channel, in that order, zero-padded when it has fewer.
+
+    ``forward(feat, graph)`` takes ``feat (N, F)`` float32 and returns
+    ``(batch_size, k * F)`` (``(1, k * F)`` for a plain graph),
+    differentiable in ``feat``. The selection and the row copy are one HIP
+    segment top-k (``kernel.segment_topk`` with ``sortby=-1``). The sort of
+    the ``F`` channels inside each node's row stays ``torch.sort(dim=-1)``: it
+    orders values within a row, not rows within a graph, so it is no segment
+    operation."""
+
+    def __init__(self, k):
+        super(SortPooling, self).__init__()
+        self.k = k
+
+    def forward(self, feat, graph):
+        feat, _ = torch.sort(feat, dim=-1)
+        segs = _topk_segments(graph, "nodes", feat.shape[0])
+        values, _ = kernel.segment_topk(feat, segs, self.k, sortby=-1)
+        return values.reshape(values.shape[0], -1)

@@ -535,6 +535,66 @@ int dglhip_segment_reduce_bwd_host(int reduce_op, int64_t num_segments, int64_t 
                                    float* dx, float* dw, int num_threads);
 
 /* ------------------------------------------------------------------------ */
+/* Segment top-k (csrc/segment_topk.hip): per segment, the first k rows in   */
+/* sorted order; the reference's topk_nodes / topk_edges and SortPooling     */
+/* (which pad every graph to the longest and call the framework's topk).     */
+/* x, offsets, ldx as for the segment reduction; 1 <= k <=                   */
+/* DGLHIP_TOPK_CHUNK (a larger k returns -1 with a message).                 */
+/* - sortby = -1: every column is ranked on its own. values float32 and      */
+/*   indices int64 are [num_segments, k, feat_len] packed: values[s, j, f]   */
+/*   is the j-th element of column f of segment s, indices[s, j, f] its row  */
+/*   within the segment (0-based).                                           */
+/* - sortby = c in [0, feat_len): whole rows are ranked by column c. values  */
+/*   [num_segments, k, feat_len] holds the selected rows, indices            */
+/*   [num_segments, k] their rows within the segment.                        */
+/* Total order: that of a stable sort. descending != 0: NaN first, then      */
+/* decreasing value; descending == 0: increasing value, NaN last. +0.0 and   */
+/* -0.0 compare equal, all NaNs compare equal, and among equal keys the      */
+/* lower row comes first. Values are moved, not computed: the output bits    */
+/* are the input bits (sign of zero, NaN payloads). A segment of n < k rows  */
+/* fills slots j >= n with +0.0 and index -1. The order is strict, so host   */
+/* and device give identical bits however the device cuts long segments:     */
+/* segments of more than DGLHIP_TOPK_CHUNK rows are ranked chunk by chunk    */
+/* and the chunks' best k merged by a second launch.                         */
+/* ------------------------------------------------------------------------ */
+#define DGLHIP_TOPK_CHUNK 2048
+/* Bytes of the device form's workspace (0: none needed). */
+int64_t dglhip_segment_topk_workspace_bytes(int64_t num_segments, int64_t num_rows,
+                                            int64_t feat_len, int64_t k, int descending,
+                                            int64_t sortby);
+/* Device form: all pointers are device pointers; one launch, plus the merge
+ * launch when a segment may be longer than a chunk. max_segment_rows: the
+ * longest segment if the caller knows it from host-side sizes (<=
+ * DGLHIP_TOPK_CHUNK skips the chunk work; it must not be understated), -1 if
+ * not. num_rows < 2^32 - 1. No host sync, no allocation, no atomics;
+ * out-of-range offsets are clamped to [0, num_rows], never followed. */
+int dglhip_segment_topk_device(int64_t num_segments, int64_t num_rows, int64_t feat_len,
+                               int64_t k, int descending, int64_t sortby,
+                               const int64_t* offsets, const float* x, int64_t ldx,
+                               float* values, int64_t* indices, int64_t max_segment_rows,
+                               void* workspace, void* stream);
+/* Host form (thread pool over the segments and columns); offsets validated
+ * as by dglhip_segment_reduce_host. */
+int dglhip_segment_topk_host(int64_t num_segments, int64_t num_rows, int64_t feat_len,
+                             int64_t k, int descending, int64_t sortby, const int64_t* offsets,
+                             const float* x, int64_t ldx, float* values, int64_t* indices,
+                             int num_threads);
+/* Backward (dx: num_rows x feat_len packed, dy shaped like values, indices
+ * the forward's): dx[offsets[s] + indices[s, j, f], f] = dy[s, j, f] for
+ * sortby = -1, dx[offsets[s] + indices[s, j], :] = dy[s, j, :] for sortby =
+ * c, slots of index -1 contribute nothing, dx is +0.0 everywhere else. The
+ * indices of a column are distinct, so every dx element is written exactly
+ * once: no atomics. */
+int dglhip_segment_topk_bwd_device(int64_t num_segments, int64_t num_rows, int64_t feat_len,
+                                   int64_t k, int descending, int64_t sortby,
+                                   const int64_t* offsets, const float* dy,
+                                   const int64_t* indices, float* dx, void* stream);
+int dglhip_segment_topk_bwd_host(int64_t num_segments, int64_t num_rows, int64_t feat_len,
+                                 int64_t k, int descending, int64_t sortby,
+                                 const int64_t* offsets, const float* dy,
+                                 const int64_t* indices, float* dx, int num_threads);
+
+/* ------------------------------------------------------------------------ */
 /* Edge softmax (csrc/edge_softmax.hip): the softmax of per-edge scores over */
 /* the edges of each node, and over the nodes or edges of each graph of a    */
 /* batch. The rows of a CSR are the groups: indptr int64[num_rows + 1],      */
