@@ -1,5 +1,5 @@
 // Device helpers of the fused attention kernels (dot_attention.hip,
-// gatv2_attention.hip): a lane's vector accesses, the xor butterfly that sums
+// gatv2_attention.hip, through attention_walk.h): a lane's vector accesses, the xor butterfly that sums
 // across the lanes of a head, and the hand-out of a row's column ids in
 // batches. Both units compute their per-edge sums with these, in a fixed
 // order: the same bits in every kernel that recomputes a score.

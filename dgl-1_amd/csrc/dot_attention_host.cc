@@ -5,38 +5,15 @@
 // maximum per row instead of one per batch, another order of the dot
 // products.
 #include "../../include/dgl_hip.h"
-#include "common.h"
+#include "attention_host.h"
 
 #include <cmath>
-#include <limits>
 
 namespace dglhip {
 
 namespace {
 
-void check_csr(int64_t R, int64_t C, int64_t nnz, const int64_t* indptr, const int32_t* indices) {
-  DGLHIP_CHECK(indptr != nullptr, "indptr is null");
-  DGLHIP_CHECK(indptr[0] == 0, "indptr must start at 0, got " << indptr[0]);
-  for (int64_t r = 0; r < R; ++r)
-    DGLHIP_CHECK(indptr[r + 1] >= indptr[r], "indptr decreases at row " << r);
-  DGLHIP_CHECK(indptr[R] == nnz, "indptr ends at " << indptr[R] << ", expected the " << nnz
-                                                   << " slots");
-  DGLHIP_CHECK(nnz == 0 || indices != nullptr, "indices is null");
-  for (int64_t k = 0; k < nnz; ++k)
-    DGLHIP_CHECK(indices[k] >= 0 && indices[k] < C, "column " << indices[k] << " of slot " << k
-                                                              << " out of range");
-}
-
-// torch's max: a NaN on either side wins
-inline float nanmax(float a, float b) { return (a > b || a != a) ? a : b; }
-
 inline float clamp_score(float s, float lo, float hi) { return s < lo ? lo : (s > hi ? hi : s); }
-
-inline float dot(const float* x, const float* y, int64_t D) {
-  float t = 0.0f;
-  for (int64_t d = 0; d < D; ++d) t += x[d] * y[d];
-  return t;
-}
 
 struct Score {
   float scale, lo, hi;
@@ -47,8 +24,6 @@ struct Score {
     return (raw < lo || raw > hi) ? 0.0f : e * (dp - delta) * scale;
   }
 };
-
-int threads_of(int num_threads) { return num_threads > 0 ? num_threads : default_num_threads(); }
 
 }  // namespace
 
@@ -69,34 +44,10 @@ int dglhip_dot_attention_host(int64_t num_rows, int64_t num_cols, int64_t nnz, i
   if (num_rows == 0 || F == 0) return 0;
   DGLHIP_CHECK(q && out && lse && (nnz == 0 || (k && v)), "null pointer argument");
   parallel_for(num_rows, threads_of(num_threads), [&](int64_t r0, int64_t r1, int) {
-    std::vector<float> s;
-    for (int64_t r = r0; r < r1; ++r) {
-      const int64_t beg = indptr[r], end = indptr[r + 1];
-      s.resize(end - beg);
-      for (int64_t h = 0; h < H; ++h) {
-        float* o = out + r * F + h * D;
-        for (int64_t d = 0; d < D; ++d) o[d] = 0.0f;
-        if (beg == end) {
-          lse[r * H + h] = 0.0f;
-          continue;
-        }
-        const float* qr = q + r * F + h * D;
-        float m = -std::numeric_limits<float>::infinity();
-        for (int64_t j = beg; j < end; ++j) {
-          s[j - beg] = clamp_score(dot(qr, k + indices[j] * F + h * D, D) * scale, lo, hi);
-          m = nanmax(m, s[j - beg]);
-        }
-        float l = 0.0f;
-        for (int64_t j = beg; j < end; ++j) {
-          const float e = std::exp(s[j - beg] - m);
-          const float* vu = v + indices[j] * F + h * D;
-          l += e;
-          for (int64_t d = 0; d < D; ++d) o[d] += e * vu[d];
-        }
-        for (int64_t d = 0; d < D; ++d) o[d] = o[d] / l;
-        lse[r * H + h] = m + std::log(l);
-      }
-    }
+    softmax_aggregate_rows(r0, r1, H, D, indptr, indices, v, out, lse,
+                           [&](int64_t r, int64_t h, int64_t j) {
+      return clamp_score(dot(q + r * F + h * D, k + indices[j] * F + h * D, D) * scale, lo, hi);
+    });
   }, nnz * F > 32768 ? 2 : num_rows + 1);
   API_END();
 }

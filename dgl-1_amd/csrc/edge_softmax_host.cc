@@ -1,8 +1,9 @@
 // Edge softmax on the host: the semantics of edge_softmax.hip, one sequential
 // pass per row on the thread pool (the rows split over the workers). The last
 // bits differ from the device's: another expf, another order of the row sum.
+// (nanmax is attention_host.h's.)
 #include "../../include/dgl_hip.h"
-#include "common.h"
+#include "attention_host.h"
 
 #include <cmath>
 #include <limits>
@@ -26,9 +27,6 @@ void check_eid(int64_t nnz, const int64_t* eid) {
     DGLHIP_CHECK(eid[k] >= 0 && eid[k] < nnz, "edge id " << eid[k] << " of slot " << k
                                                          << " out of range");
 }
-
-// torch's max: a NaN on either side wins
-inline float nanmax(float a, float b) { return (a > b || a != a) ? a : b; }
 
 }  // namespace
 

@@ -26,23 +26,17 @@
 // tile could hold. The kernels are bound by the gathers and stay on the
 // vector unit.
 //
-// Lane map: dot_attention.hip's. A lane holds VEC consecutive features of one
-// head (4 with 16-byte accesses when D % 4 == 0 and every tensor is 16-byte
-// aligned, else 2, else 1), a head takes LPH lanes, the power of two that
-// covers D / VEC (lanes past D hold zeros, of attn too), a wave covers
-// 64 / LPH heads, more heads are further head tiles: a wave is one (row, head
-// tile). fd[r] and attn[h] (in the transposed walk fs[u] and attn[h]) are
-// loaded once per wave and stay in registers. A score is summed per lane over
-// its VEC features (lane_score: one product, then fmas, in feature order) and
-// across the head's lanes by head_sum's butterfly (attention_lanes.h); the
+// Lane map: attention_walk.h's, as dot_attention.hip. fd[r] and attn[h] (in the
+// transposed walk fs[u] and attn[h]) are loaded once per wave and stay in
+// registers; lanes past D hold zeros, of attn too. A score is summed per lane
+// over its VEC features (lane_score: one product, then fmas, in feature order)
+// and across the head's lanes by head_sum's butterfly (attention_lanes.h); the
 // three walks use the same chain, so they get the same bits for s_j.
 //
-// The walk. Up to 64 column ids per coalesced trip, handed out lane to lane
-// (batch_ids); the slots run in batches whose single gather per slot (three
-// in the transposed walk: fd, dout, and lse with delta) is issued before
-// first use. Forward, per batch: the elementwise scores, one butterfly, one
-// rescale expf(m - m') of the running sum and the VEC accumulators, then per
-// slot in slot order p = expf(s - m'), l += p, acc = fma(p, fs_j, acc). The
+// The walk: attention_walk.h's; the slots run in batches whose single gather
+// per slot (three in the transposed walk: fd, dout, and lse with delta) is
+// issued before first use. Forward, per batch: the elementwise scores, one
+// butterfly, then the online softmax's step with fs_j as the value row. The
 // batch sizes (DGLHIP_GATV2_BATCH*) are the largest of 8, 16, 32 (the sizes
 // that divide a trip's 64 ids) whose resource report shows no scratch in any
 // instantiation and, at VEC 4, the 4 waves per SIMD of dot_attention.hip's
@@ -51,11 +45,8 @@
 // halve its waves, the same rows in flight) and 8 in the dfs walk (two rows
 // a slot).
 //
-// Long rows. A row of more than DGLHIP_GATV2_CHUNK slots is cut where it
-// crosses the multiples of the chunk (row_pieces.h), a piece a wave. Forward:
-// a piece leaves (m, l, acc[D]) per head in the workspace and the wave of the
-// row's first piece merges them in block order. Backward: the pieces are
-// partial sums, added in block order.
+// Long rows: attention_walk.h's pieces, cut at the multiples of
+// DGLHIP_GATV2_CHUNK.
 //
 // dattn is the one output that sums across rows. Every wave of the dfd walk
 // leaves its partial (of its schedule item, or of its piece; zeros where it
@@ -65,10 +56,7 @@
 //
 // No atomics; every output element has one writer: the same bits on every call.
 #include "../../include/dgl_hip.h"
-#include "attention_lanes.h"
-#include "common.h"
-#include "launch.h"
-#include "row_pieces.h"
+#include "attention_walk.h"
 
 #include <hip/hip_runtime.h>
 
@@ -78,23 +66,14 @@ namespace dglhip {
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
 constexpr int64_t kChunk = DGLHIP_GATV2_CHUNK;
 constexpr int kBatchFwd = DGLHIP_GATV2_BATCH;
 constexpr int kBatchDfd = DGLHIP_GATV2_BATCH_DFD;
 constexpr int kBatchDfs = DGLHIP_GATV2_BATCH_DFS;
 constexpr int64_t kParts = 1024;  // ranges of dattn partials summed side by side
 
-struct Args {
-  int64_t R, C, nnz, H, D;  // rows and columns of the CSR the kernel walks
-  int64_t G;                // blocks of kChunk slots (0: no row is longer than a chunk)
-  int64_t tiles;            // head tiles per row
-  int lph_shift;            // log2 of the lanes per head
+struct Args : Walk {
   float slope;
-  const int64_t* indptr;
-  const int32_t* indices;
-  const int32_t* row_order;
   const float *fs, *fd, *attn;  // fs by source, fd by destination, attn (H, D)
   const float *dout, *out;      // by destination (backward)
   const float *lse, *delta;     // (destinations, H), read (backward)
@@ -105,55 +84,6 @@ struct Args {
   float* dattn;
   int64_t slots, per, nparts;   // dattn partials, slots a range, ranges
 };
-
-// a lane's place: VEC features of one head
-struct Place {
-  int64_t head;   // its head, and one that exists (for the loads of idle heads)
-  int64_t hsafe;
-  int64_t foff;   // head * D + its first feature
-  bool live;      // it holds features
-  bool first;     // the first lane of a head that exists
-};
-
-template <int VEC>
-__device__ __forceinline__ Place place_of(const Args& a, int64_t tile, int lane) {
-  Place p;
-  const int sub = lane & ((1 << a.lph_shift) - 1);
-  p.head = tile * (64 >> a.lph_shift) + (lane >> a.lph_shift);
-  const bool headok = p.head < a.H;
-  p.hsafe = headok ? p.head : 0;
-  p.live = headok && int64_t(sub) * VEC < a.D;
-  p.first = headok && sub == 0;
-  p.foff = p.head * a.D + int64_t(sub) * VEC;
-  return p;
-}
-
-// a lane's features of row `node` of a (nodes, H, D) tensor; zeros in idle lanes
-template <int VEC>
-__device__ __forceinline__ void row_load(const float* base, int64_t node, int64_t F,
-                                         const Place& p, float (&v)[VEC]) {
-  if (p.live) {
-    load_vec<VEC>(base + node * F + p.foff, v);
-  } else {
-#pragma unroll
-    for (int c = 0; c < VEC; ++c) v[c] = 0.0f;
-  }
-}
-
-template <int VEC>
-__device__ __forceinline__ void zero(float (&v)[VEC]) {
-#pragma unroll
-  for (int c = 0; c < VEC; ++c) v[c] = 0.0f;
-}
-
-// a lane's share of a dot product: one product, then fmas, in feature order
-template <int VEC>
-__device__ __forceinline__ float lane_dot(const float (&x)[VEC], const float (&y)[VEC]) {
-  float t = x[0] * y[0];
-#pragma unroll
-  for (int c = 1; c < VEC; ++c) t = __builtin_fmaf(x[c], y[c], t);
-  return t;
-}
 
 __device__ __forceinline__ float lrelu(float z, float slope) { return z > 0.0f ? z : slope * z; }
 
@@ -173,50 +103,6 @@ __device__ __forceinline__ float lane_score(const float (&fs)[VEC], const float 
   return t;
 }
 
-// what a wave finds at its place in the schedule
-enum Found { kPast, kSkip, kWalk };  // past the end | nothing to walk here | slots to walk
-
-// the wave's (item of the schedule, head tile); false past the end
-__device__ __forceinline__ bool wave_item(const Args& a, int64_t items, int64_t& item,
-                                          int64_t& tile) {
-  const int64_t id = block_linear() * kWaves +
-                     __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
-  item = id / a.tiles;
-  tile = id - item * a.tiles;
-  return item < items;
-}
-
-// the wave's row, item `it` of the schedule, of at most a chunk of slots
-// (kSkip: a longer one, which is the pieces', or a row_order entry off the rows)
-__device__ __forceinline__ Found wave_row(const Args& a, int64_t& it, int64_t& row, int64_t& tile,
-                                          int64_t& beg, int64_t& end) {
-  if (!wave_item(a, a.R, it, tile)) return kPast;
-  row = a.row_order ? a.row_order[it] : it;
-  row = __builtin_amdgcn_readfirstlane(static_cast<int>(row));
-  if (row < 0 || row >= a.R) return kSkip;
-  beg = clampi(a.indptr[row], 0, a.nnz);
-  end = clampi(a.indptr[row + 1], beg, a.nnz);
-  return (a.G > 0 && end - beg > kChunk) ? kSkip : kWalk;
-}
-
-struct Piece {
-  int64_t item, row, k0, k1, first, last;
-};
-
-// the wave's piece of a long row (kSkip: the item holds none)
-__device__ __forceinline__ Found wave_piece(const Args& a, int lane, Piece& pc, int64_t& tile) {
-  if (!wave_item(a, 2 * a.G, pc.item, tile)) return kPast;
-  if (!long_row_piece(a.indptr, a.R, a.nnz, a.G, kChunk, pc.item, lane, pc.row, pc.k0, pc.k1,
-                      pc.first, pc.last))
-    return kSkip;
-  pc.row = uniform64(pc.row);
-  pc.k0 = uniform64(pc.k0);
-  pc.k1 = uniform64(pc.k1);
-  pc.first = uniform64(pc.first);
-  pc.last = uniform64(pc.last);
-  return kWalk;
-}
-
 // ---------------------------------------------------------------------------
 // forward
 // ---------------------------------------------------------------------------
@@ -233,43 +119,15 @@ __device__ __forceinline__ void fwd_range(const Args& a, const Place& p, int lan
 #pragma unroll
     for (int i = 0; i < kBatchFwd; ++i) s[i] = lane_score<VEC>(ff[i], fdv, atv, a.slope);
     head_sum<kBatchFwd>(s, a.lph_shift);
-    float mn = m;
-#pragma unroll
-    for (int i = 0; i < kBatchFwd; ++i) {
-      if (i < n) mn = nanmax(mn, s[i]);
-    }
-    const float r = expf(m - mn);  // the first batch: expf(-inf) = 0 on zeros
-    l = l * r;
-#pragma unroll
-    for (int c = 0; c < VEC; ++c) acc[c] = acc[c] * r;
-#pragma unroll
-    for (int i = 0; i < kBatchFwd; ++i) {
-      if (i < n) {
-        const float e = expf(s[i] - mn);
-        l = l + e;
-#pragma unroll
-        for (int c = 0; c < VEC; ++c) acc[c] = __builtin_fmaf(e, ff[i][c], acc[c]);
-      }
-    }
-    m = mn;
+    softmax_step<kBatchFwd, VEC>(s, n, ff, m, l, acc);
   });
-}
-
-template <int VEC>
-__device__ __forceinline__ void fwd_store(const Args& a, const Place& p, int64_t row, bool empty,
-                                          float m, float l, const float (&acc)[VEC]) {
-  float o[VEC];
-#pragma unroll
-  for (int c = 0; c < VEC; ++c) o[c] = empty ? 0.0f : acc[c] / l;
-  if (p.live) store_vec<VEC>(a.o0 + row * a.H * a.D + p.foff, o);
-  if (p.first) a.stat[row * a.H + p.head] = empty ? 0.0f : m + logf(l);
 }
 
 template <int VEC>
 __global__ __launch_bounds__(kThreads) void gatv2_fwd_rows_kernel(Args a) {
   const int lane = threadIdx.x & 63;
   int64_t it, row, tile, beg, end;
-  if (wave_row(a, it, row, tile, beg, end) != kWalk) return;  // the whole wave
+  if (wave_row<kChunk>(a, it, row, tile, beg, end) != kWalk) return;  // the whole wave
   const Place p = place_of<VEC>(a, tile, lane);
   float fdv[VEC], atv[VEC], acc[VEC];
   row_load<VEC>(a.fd, row, a.H * a.D, p, fdv);
@@ -285,7 +143,7 @@ __global__ __launch_bounds__(kThreads) void gatv2_fwd_piece_kernel(Args a) {
   const int lane = threadIdx.x & 63;
   Piece pc;
   int64_t tile;
-  if (wave_piece(a, lane, pc, tile) != kWalk) return;  // the whole wave
+  if (wave_piece<kChunk>(a, lane, pc, tile) != kWalk) return;  // the whole wave
   const Place p = place_of<VEC>(a, tile, lane);
   float fdv[VEC], atv[VEC], acc[VEC];
   row_load<VEC>(a.fd, pc.row, a.H * a.D, p, fdv);
@@ -300,60 +158,25 @@ __global__ __launch_bounds__(kThreads) void gatv2_fwd_piece_kernel(Args a) {
   }
 }
 
-// The wave of a long row's first piece merges the row's pieces, in block
-// order: the first one, then the items 2 g of the blocks up to the last.
 template <int VEC>
 __global__ __launch_bounds__(kThreads) void gatv2_fwd_combine_kernel(Args a) {
-  const int lane = threadIdx.x & 63;
-  Piece pc;
-  int64_t tile;
-  if (wave_piece(a, lane, pc, tile) != kWalk || pc.item != pc.first) return;
-  const Place p = place_of<VEC>(a, tile, lane);
-  const int64_t F = a.H * a.D;
-  const float* ml = a.wsml + p.hsafe * 2;
-  float m = ml[pc.first * a.H * 2];
-  for (int64_t g = (pc.first >> 1) + 1; g <= pc.last; ++g) m = nanmax(m, ml[2 * g * a.H * 2]);
-  float l = 0.0f, acc[VEC];
-  zero<VEC>(acc);
-  for (int64_t g = pc.first >> 1; g <= pc.last; ++g) {
-    const int64_t item = g == (pc.first >> 1) ? pc.first : 2 * g;
-    const float mg = ml[item * a.H * 2], lg = ml[item * a.H * 2 + 1];
-    float pa[VEC];
-    row_load<VEC>(a.ws0, item, F, p, pa);
-    // a piece of only -inf beside a larger maximum adds nothing (its own sum
-    // is NaN: -inf - -inf); when every piece is one, l stays 0 and out is NaN
-    if (mg != -INFINITY) {
-      const float w = expf(mg - m);
-      l = __builtin_fmaf(lg, w, l);
-#pragma unroll
-      for (int c = 0; c < VEC; ++c) acc[c] = __builtin_fmaf(w, pa[c], acc[c]);
-    }
-  }
-  fwd_store<VEC>(a, p, pc.row, false, m, l, acc);
+  fwd_combine<VEC, kChunk>(a);
 }
 
 // ---------------------------------------------------------------------------
 // backward over the forward CSR: delta, dfd and the dattn partials
 // ---------------------------------------------------------------------------
-// what a destination's wave holds: fd, dout, lse and delta = <dout, out> of its head
+// what a destination's wave holds: fd, and dout, lse and delta of its head
 template <int VEC>
-struct DstRow {
-  float fd[VEC], dout[VEC];
-  float lse, delta;
+struct DstRow : DstGrad<VEC> {
+  float fd[VEC];
 };
 
 template <int VEC>
 __device__ __forceinline__ DstRow<VEC> dst_row(const Args& a, const Place& p, int64_t row) {
   DstRow<VEC> d;
-  const int64_t F = a.H * a.D;
-  float ov[VEC], t[1];
-  row_load<VEC>(a.fd, row, F, p, d.fd);
-  row_load<VEC>(a.dout, row, F, p, d.dout);
-  row_load<VEC>(a.out, row, F, p, ov);
-  d.lse = a.lse[row * a.H + p.hsafe];
-  t[0] = lane_dot<VEC>(d.dout, ov);
-  head_sum<1>(t, a.lph_shift);
-  d.delta = t[0];
+  row_load<VEC>(a.fd, row, a.H * a.D, p, d.fd);
+  dst_grad<VEC>(a, p, row, d);
   return d;
 }
 
@@ -404,7 +227,7 @@ template <int VEC>
 __global__ __launch_bounds__(kThreads) void gatv2_dfd_rows_kernel(Args a) {
   const int lane = threadIdx.x & 63;
   int64_t it, row, tile, beg, end;
-  const Found found = wave_row(a, it, row, tile, beg, end);
+  const Found found = wave_row<kChunk>(a, it, row, tile, beg, end);
   if (found == kPast) return;  // the whole wave
   const Place p = place_of<VEC>(a, tile, lane);
   const int64_t F = a.H * a.D;
@@ -428,7 +251,7 @@ __global__ __launch_bounds__(kThreads) void gatv2_dfd_piece_kernel(Args a) {
   const int lane = threadIdx.x & 63;
   Piece pc;
   int64_t tile;
-  const Found found = wave_piece(a, lane, pc, tile);
+  const Found found = wave_piece<kChunk>(a, lane, pc, tile);
   if (found == kPast) return;  // the whole wave
   const Place p = place_of<VEC>(a, tile, lane);
   const int64_t F = a.H * a.D;
@@ -446,24 +269,9 @@ __global__ __launch_bounds__(kThreads) void gatv2_dfd_piece_kernel(Args a) {
   if (p.live) store_vec<VEC>(a.part + (a.R + pc.item) * F + p.foff, da);
 }
 
-// The backward's pieces are partial sums: the wave of a long row's first
-// piece adds them in block order.
 template <int VEC>
 __global__ __launch_bounds__(kThreads) void gatv2_sum_pieces_kernel(Args a) {
-  const int lane = threadIdx.x & 63;
-  Piece pc;
-  int64_t tile;
-  if (wave_piece(a, lane, pc, tile) != kWalk || pc.item != pc.first) return;
-  const Place p = place_of<VEC>(a, tile, lane);
-  const int64_t F = a.H * a.D;
-  float s0[VEC], t[VEC];
-  row_load<VEC>(a.ws0, pc.first, F, p, s0);
-  for (int64_t g = (pc.first >> 1) + 1; g <= pc.last; ++g) {
-    row_load<VEC>(a.ws0, 2 * g, F, p, t);
-#pragma unroll
-    for (int c = 0; c < VEC; ++c) s0[c] = s0[c] + t[c];
-  }
-  if (p.live) store_vec<VEC>(a.o0 + pc.row * F + p.foff, s0);
+  sum_pieces<VEC, 1, kChunk>(a);
 }
 
 // dattn, first level: a thread per element (h, d) adds the partials of range
@@ -542,11 +350,11 @@ __global__ __launch_bounds__(kThreads) void gatv2_dfs_kernel(Args a) {
   int64_t row, tile, beg, end, at;
   if constexpr (PIECE) {
     Piece pc;
-    if (wave_piece(a, lane, pc, tile) != kWalk) return;  // the whole wave
+    if (wave_piece<kChunk>(a, lane, pc, tile) != kWalk) return;  // the whole wave
     row = pc.row; beg = pc.k0; end = pc.k1; at = pc.item;
   } else {
     int64_t it;
-    if (wave_row(a, it, row, tile, beg, end) != kWalk) return;
+    if (wave_row<kChunk>(a, it, row, tile, beg, end) != kWalk) return;
     at = row;
   }
   const Place p = place_of<VEC>(a, tile, lane);
@@ -565,14 +373,6 @@ __global__ __launch_bounds__(kThreads) void gatv2_dfs_kernel(Args a) {
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
-bool aligned(const void* p, uintptr_t n) { return (reinterpret_cast<uintptr_t>(p) & (n - 1)) == 0; }
-
-int64_t num_blocks(int64_t nnz) { return (nnz + kChunk - 1) / kChunk; }
-
-bool has_pieces(int64_t nnz, int64_t max_row_len) {
-  return nnz > kChunk && (max_row_len < 0 || max_row_len > kChunk);
-}
-
 // The workspace, in floats: the pieces' rows [0, ml), their (m, l) pairs
 // [ml, part), and for the backward the dattn partials [part, part2) and the
 // ranges' sums [part2, total). One set of pieces serves both walks of the
@@ -586,8 +386,8 @@ Layout layout_of(int64_t R, int64_t nnz, int64_t H, int64_t D, int64_t max_row_l
                  int64_t max_col_len, bool backward) {
   Layout w = {};
   const int64_t F = H * D;
-  w.Gq = has_pieces(nnz, max_row_len) ? num_blocks(nnz) : 0;
-  w.G = (w.Gq || (backward && has_pieces(nnz, max_col_len))) ? num_blocks(nnz) : 0;
+  w.Gq = has_pieces(nnz, max_row_len, kChunk) ? num_blocks(nnz, kChunk) : 0;
+  w.G = (w.Gq || (backward && has_pieces(nnz, max_col_len, kChunk))) ? num_blocks(nnz, kChunk) : 0;
   w.ml = 2 * w.G * F;
   w.part = w.ml + 4 * w.G * H;
   w.slots = backward ? R + 2 * w.Gq : 0;
@@ -595,28 +395,6 @@ Layout layout_of(int64_t R, int64_t nnz, int64_t H, int64_t D, int64_t max_row_l
   w.total = w.part2 + (backward ? kParts * F : 0);
   return w;
 }
-
-// the widest access every row of every tensor allows
-int vec_of(int64_t D, std::initializer_list<const void*> ptrs) {
-  int V = D % 4 == 0 ? 4 : (D % 2 == 0 ? 2 : 1);
-  for (const void* p : ptrs) {
-    while (V > 1 && p && !aligned(p, 4 * V)) V >>= 1;
-  }
-  return V;
-}
-
-// fills the lane map of `a` for VEC features a lane
-void lane_map(Args& a, int V) {
-  const int64_t need = (a.D + V - 1) / V;
-  DGLHIP_CHECK(need <= 64, "a head of " << a.D << " features is wider than the fused path's "
-                                        << 64 * V << " at " << 4 * V << "-byte accesses");
-  a.lph_shift = 0;
-  while ((int64_t(1) << a.lph_shift) < need) ++a.lph_shift;
-  const int64_t hpw = 64 >> a.lph_shift;
-  a.tiles = (a.H + hpw - 1) / hpw;
-}
-
-dim3 waves_grid(int64_t waves) { return grid_1d((waves + kWaves - 1) / kWaves); }
 
 template <int V>
 void forward_v(const Args& a, hipStream_t stream) {
@@ -657,12 +435,6 @@ void backward_v(const Args& aq, const Args& at, hipStream_t stream) {
     hipLaunchKernelGGL((gatv2_sum_pieces_kernel<V>), pgrid, dim3(kThreads), 0, stream, at);
   }
   DGLHIP_CHECK(hipGetLastError() == hipSuccess, "gatv2 attention dfs launch failed");
-}
-
-void check_sizes(int64_t R, int64_t C, int64_t nnz, int64_t H, int64_t D) {
-  DGLHIP_CHECK(R >= 0 && C >= 0 && nnz >= 0 && H >= 0 && D >= 0, "negative size");
-  DGLHIP_CHECK(R < (int64_t(1) << 31) && C < (int64_t(1) << 31), "more than 2^31 - 1 nodes");
-  DGLHIP_CHECK(nnz == 0 || C > 0, "slots without columns");
 }
 
 }  // namespace
@@ -706,9 +478,7 @@ int dglhip_gatv2_attention_device(int64_t num_rows, int64_t num_cols, int64_t nn
   const int V = vec_of(head_dim, {fs, fd, attn, out, a.G ? workspace : nullptr});
   lane_map(a, V);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (V == 4) forward_v<4>(a, st);
-  else if (V == 2) forward_v<2>(a, st);
-  else forward_v<1>(a, st);
+  with_vec(V, [&](auto v) { forward_v<decltype(v)::value>(a, st); });
   API_END();
 }
 
@@ -746,14 +516,12 @@ int dglhip_gatv2_attention_bwd_device(int64_t num_rows, int64_t num_cols, int64_
   at.R = num_cols; at.C = num_rows;
   at.indptr = t_indptr; at.indices = t_indices; at.row_order = t_row_order;
   at.delta = delta; at.o0 = dfs; at.stat = nullptr;
-  at.G = has_pieces(nnz, max_col_len) ? w.G : 0;
+  at.G = has_pieces(nnz, max_col_len, kChunk) ? w.G : 0;
   const int V = vec_of(head_dim, {fs, fd, attn, out, dout, dfs, dfd, workspace});
   lane_map(aq, V);
   lane_map(at, V);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (V == 4) backward_v<4>(aq, at, st);
-  else if (V == 2) backward_v<2>(aq, at, st);
-  else backward_v<1>(aq, at, st);
+  with_vec(V, [&](auto v) { backward_v<decltype(v)::value>(aq, at, st); });
   API_END();
 }
 

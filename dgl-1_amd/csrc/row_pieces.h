@@ -1,6 +1,7 @@
 // Long rows cut into pieces, shared by the kernels that walk a CSR row by row
-// (edge_softmax.hip, dot_attention.hip, gatv2_attention.hip). A row of more than `chunk` slots is
-// cut where it crosses the multiples of the chunk: block g is slots
+// (edge_softmax.hip, and through attention_walk.h dot_attention.hip and
+// gatv2_attention.hip). A row of more than `chunk` slots is cut where it
+// crosses the multiples of the chunk: block g is slots
 // [g chunk, (g + 1) chunk), and it meets at most two long rows, the one that
 // holds its first slot (item 2 g) and one that starts inside it (item
 // 2 g + 1). The geometry comes from the sizes alone: 2 G items for G blocks.

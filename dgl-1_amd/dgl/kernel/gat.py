@@ -647,13 +647,31 @@ DOT_ATTENTION_CHUNK = 1024  # DGLHIP_DOT_ATTENTION_CHUNK: a longer row is cut in
 DOT_ATTENTION_BATCH = 8  # DGLHIP_DOT_ATTENTION_BATCH: slots per rescale of the running sums
 
 
-def _dot_attention_vec(D, tensors):
-    """Floats per access of the fused kernels (their gate: dot_attention.hip)."""
+def _attention_vec(D, tensors):
+    """Floats per access of the fused kernels (their gate: attention_walk.h)."""
     V = 4 if D % 4 == 0 else (2 if D % 2 == 0 else 1)
     for t in tensors:
         while V > 1 and t.data_ptr() % (4 * V):
             V >>= 1
     return V
+
+
+def _attention_head(fwd, x):
+    """The leading arguments of the fused attention entry points for the
+    (rows, H, D) destination tensor ``x``, and a (rows, H) float32 tensor for
+    lse or delta."""
+    R, H, D = x.shape
+    head = (R, fwd.num_cols, fwd.nnz, H, D, ptr(fwd.indptr), ptr(fwd.indices))
+    return head, torch.empty(R, H, dtype=torch.float32, device=x.device)
+
+
+def _attention_grad(dout):
+    dout = _f32c(dout)
+    if dout.data_ptr() % 16:
+        # a gradient that arrives as a view at an odd offset would narrow
+        # the accesses below what the forward's gate found for this D
+        dout = dout.clone()
+    return dout
 
 
 def _dot_attention_workspace(csrs, H, D, dev):
@@ -674,8 +692,7 @@ class _DotAttention(torch.autograd.Function):
         R, H, D = q.shape
         dev = q.device
         out = torch.empty_like(q)
-        lse = torch.empty(R, H, dtype=torch.float32, device=dev)
-        head = (R, fwd.num_cols, fwd.nnz, H, D, ptr(fwd.indptr), ptr(fwd.indices))
+        head, lse = _attention_head(fwd, q)
         if dev.type == "cuda":
             ws = _dot_attention_workspace((fwd,), H, D, dev)
             check_call(LIB.dglhip_dot_attention_device(*(head + (
@@ -694,14 +711,9 @@ class _DotAttention(torch.autograd.Function):
         fwd, bwd = ctx.adj.fwd, ctx.adj.bwd
         R, H, D = q.shape
         dev = q.device
-        dout = _f32c(dout)
-        if dout.data_ptr() % 16:
-            # a gradient that arrives as a view at an odd offset would narrow
-            # the accesses below what the forward's gate found for this D
-            dout = dout.clone()
-        delta = torch.empty_like(lse)
+        dout = _attention_grad(dout)
+        head, delta = _attention_head(fwd, q)
         dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-        head = (R, fwd.num_cols, fwd.nnz, H, D, ptr(fwd.indptr), ptr(fwd.indices))
         mid = (ptr(q), ptr(k), ptr(v), ptr(out), ptr(lse), ptr(dout), ctx.scale, ctx.lo, ctx.hi,
                ptr(delta), ptr(dq), ptr(dk), ptr(dv))
         if dev.type == "cuda":
@@ -788,7 +800,7 @@ def dot_attention(adj, q, k, v, scale=None, clamp=None):
     if q.numel() == 0 or adj.fwd.nnz == 0:
         return torch.zeros_like(q)
     scale = float(D) ** -0.5 if scale is None else float(scale)
-    if D > 64 * _dot_attention_vec(D, (q, k, v)):
+    if D > 64 * _attention_vec(D, (q, k, v)):
         return _dot_attention_composed(adj, q, k, v, scale, clamp)
     lo, hi = (-float("inf"), float("inf")) if clamp is None else (float(clamp[0]), float(clamp[1]))
     return _DotAttention.apply(adj, scale, lo, hi, q, k, v)
@@ -824,8 +836,7 @@ class _GATv2Attention(torch.autograd.Function):
         R, H, D = fd.shape
         dev = fd.device
         out = torch.empty_like(fd)
-        lse = torch.empty(R, H, dtype=torch.float32, device=dev)
-        head = (R, fwd.num_cols, fwd.nnz, H, D, ptr(fwd.indptr), ptr(fwd.indices))
+        head, lse = _attention_head(fwd, fd)
         if dev.type == "cuda":
             ws = _gatv2_workspace(adj, H, D, dev, False)
             check_call(LIB.dglhip_gatv2_attention_device(*(head + (
@@ -844,14 +855,9 @@ class _GATv2Attention(torch.autograd.Function):
         fwd, bwd = ctx.adj.fwd, ctx.adj.bwd
         R, H, D = fd.shape
         dev = fd.device
-        dout = _f32c(dout)
-        if dout.data_ptr() % 16:
-            # a gradient that arrives as a view at an odd offset would narrow
-            # the accesses below what the forward's gate found for this D
-            dout = dout.clone()
-        delta = torch.empty_like(lse)
+        dout = _attention_grad(dout)
+        head, delta = _attention_head(fwd, fd)
         dfs, dfd, dattn = torch.empty_like(fs), torch.empty_like(fd), torch.empty_like(attn)
-        head = (R, fwd.num_cols, fwd.nnz, H, D, ptr(fwd.indptr), ptr(fwd.indices))
         mid = (ptr(fs), ptr(fd), ptr(attn), ptr(out), ptr(lse), ptr(dout), ctx.slope,
                ptr(delta), ptr(dfs), ptr(dfd), ptr(dattn))
         if dev.type == "cuda":
@@ -919,6 +925,6 @@ def gatv2_attention(adj, fs, fd, attn, negative_slope=0.2, attn_drop=0.0):
     if fd.numel() == 0 or adj.fwd.nnz == 0:
         return torch.zeros_like(fd)
     slope = float(negative_slope)
-    if attn_drop > 0 or D > 64 * _dot_attention_vec(D, (fs, fd, attn)):
+    if attn_drop > 0 or D > 64 * _attention_vec(D, (fs, fd, attn)):
         return _gatv2_attention_composed(adj, fs, fd, attn, slope, float(attn_drop))
     return _GATv2Attention.apply(adj, slope, fs, fd, attn)
