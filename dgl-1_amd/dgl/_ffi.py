@@ -241,6 +241,11 @@ def _load():
         "dglhip_segment_topk_bwd_device": (_c_int, [_c_i64] * 4 + [_c_int, _c_i64] + [_vp] * 5),
         "dglhip_segment_topk_bwd_host": (_c_int, [_c_i64] * 4 + [_c_int, _c_i64] + [_vp] * 4 +
                                          [_c_int]),
+        "dglhip_segment_knn_workspace_bytes": (_c_i64, [_c_i64] * 4),
+        "dglhip_segment_knn_device": (_c_int, [_c_i64] * 4 + [_c_int, _vp, _vp, _c_i64] +
+                                      [_vp] * 4),
+        "dglhip_segment_knn_host": (_c_int, [_c_i64] * 4 + [_c_int, _vp, _vp, _c_i64, _vp, _vp,
+                                                            _c_int]),
         "dglhip_edge_softmax_workspace_bytes": (_c_i64, [_c_i64, _c_i64, _c_i64]),
         "dglhip_edge_softmax_device": (_c_int, [_c_i64, _c_i64, _c_i64] + [_vp] * 5 +
                                        [_c_i64, _vp, _vp]),

@@ -671,8 +671,9 @@ class SubgraphIndex(_DeviceCOOIndex):
 
 
 class _DeviceLineGraphIndex(_DeviceCOOIndex):
-    """The mutable, non-multigraph index of a line graph whose edge list
-    GraphIndex.line_graph_device left on the GPU. The first mutation builds
+    """The mutable, non-multigraph index of a graph whose edge list a device
+    builder left on the GPU: GraphIndex.line_graph_device's line graph, and
+    the k-nearest-neighbour graphs of transform.py. The first mutation builds
     the native index, drops the device edge list and the caches, and goes on
     as any index does."""
 

@@ -1,5 +1,7 @@
 """The segment reduction (csrc/segment_reduce.hip) and the segment top-k
-(csrc/segment_topk.hip): the readouts of a batched graph."""
+(csrc/segment_topk.hip): the readouts of a batched graph; and the segment
+k-nearest neighbours (csrc/segment_knn.hip): the graph of a batch of point
+clouds."""
 from __future__ import absolute_import
 
 import numpy as np
@@ -15,6 +17,8 @@ from .spmm import _f32c
 # ---------------------------------------------------------------------------
 SEGMENT_CHUNK = 1024  # DGLHIP_SEGMENT_CHUNK: rows per chain of the segment reduction
 TOPK_CHUNK = 2048  # DGLHIP_TOPK_CHUNK: rows one workgroup ranks in LDS, and the largest k
+KNN_MAX_K = 64  # DGLHIP_KNN_MAX_K: the longest neighbour list of the segment kNN
+KNN_MAX_DIM = 256  # DGLHIP_KNN_MAX_DIM: the most coordinates of its points
 
 
 class SegmentOffsets(object):
@@ -298,3 +302,60 @@ def segment_topk(x, offsets, k, descending=True, sortby=None):
     values, indices = _SegmentTopk.apply(x.reshape(N, F), segs, k, 1 if descending else 0, col)
     values = values.view((B, k) + fshape)
     return values, (indices if col >= 0 else indices.view((B, k) + fshape))
+
+
+# ---------------------------------------------------------------------------
+# Segment k-nearest neighbours: knn_graph / segmented_knn_graph (csrc/segment_knn.hip)
+# ---------------------------------------------------------------------------
+def segment_knn(x, offsets, k, exclude_self=False):
+    """For every row ``i`` of every segment ``x[offsets[s] : offsets[s+1]]``
+    the ``k`` rows ``j`` of the same segment nearest to it: ``(nbr, dist)``,
+    ``nbr (N, k)`` int64 global row ids and ``dist (N, k)`` float32 squared
+    Euclidean distances, both ascending. Not differentiable.
+
+    ``x`` is ``(N, D)`` float32 (read in place through its row stride),
+    ``offsets`` what :func:`segment_reduce` takes, ``1 <= k <= KNN_MAX_K`` and
+    ``D <= KNN_MAX_DIM``; outside is an error, not another path.
+
+    In float32, ``d(i, j) = n_i + n_j - 2 <x_i, x_j>`` with ``n_i = <x_i,
+    x_i>``; a value not above zero is ``+0.0``, a NaN stays NaN, ``d(i, i)``
+    is ``+0.0`` by definition and with ``exclude_self`` the pair ``(i, i)`` is
+    no candidate. The order is ascending by ``(d, j)``, NaN last: an ascending
+    stable sort, so no tie is left to chance. A row with fewer than ``k``
+    candidates fills the remaining slots with ``-1`` and ``+inf``. On a ROCm
+    device the dot products run on the f32 MFMA and the selection in the same
+    pass: no distance matrix is written. Host and device each return the
+    exact top-k under their own float32 distances; where the arithmetic is
+    exact they agree index for index."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 2:
+        raise DGLError("segment_knn expects an (N, D) tensor of points")
+    if x.dtype != torch.float32:
+        raise DGLError("segment_knn computes in float32, got %s" % x.dtype)
+    k = int(k)
+    if k < 1 or k > KNN_MAX_K:
+        raise DGLError("segment_knn serves 1 <= k <= KNN_MAX_K = %d, got k = %d" % (KNN_MAX_K, k))
+    N, D = x.shape
+    if D > KNN_MAX_DIM:
+        raise DGLError("segment_knn serves D <= KNN_MAX_DIM = %d, got D = %d" % (KNN_MAX_DIM, D))
+    segs = _segment_offsets(offsets)
+    if segs.num_rows >= 0 and segs.num_rows != N:
+        raise DGLError("offsets end at %d, expected the %d rows" % (segs.num_rows, N))
+    B, dev = segs.num_segments, x.device
+    nbr = torch.full((N, k), -1, dtype=torch.int64, device=dev)
+    dist = torch.full((N, k), float("inf"), dtype=torch.float32, device=dev)
+    if N == 0 or B == 0:
+        return nbr, dist
+    if D == 0:  # no storage to point the library at: every distance is +0.0
+        x, D = x.new_zeros(N, 1), 1
+    off = segs.on(dev)
+    xv, ldx = _rows_view(x.detach(), D)
+    if dev.type == "cuda":
+        ws = torch.empty(LIB.dglhip_segment_knn_workspace_bytes(B, N, D, k), dtype=torch.uint8,
+                         device=dev)
+        check_call(LIB.dglhip_segment_knn_device(
+            B, N, D, k, int(bool(exclude_self)), ptr(off), ptr(xv), ldx, ptr(nbr), ptr(dist),
+            ptr(ws), _stream_of(dev)))
+    else:
+        check_call(LIB.dglhip_segment_knn_host(
+            B, N, D, k, int(bool(exclude_self)), ptr(off), ptr(xv), ldx, ptr(nbr), ptr(dist), 0))
+    return nbr, dist

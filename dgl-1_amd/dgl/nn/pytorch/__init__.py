@@ -3,8 +3,8 @@ modules the north star names (GraphConv, GATConv) and SAGEConv / RelGraphConv.""
 from __future__ import absolute_import
 
 from .gcn import GraphConvolutionLayer  # noqa: F401
-from .conv import DotGatConv, GATConv, GATv2Conv, GraphConv, RelGraphConv, SAGEConv  # noqa: F401
+from .conv import DotGatConv, EdgeConv, GATConv, GATv2Conv, GraphConv, RelGraphConv, SAGEConv  # noqa: F401
 from .linear import NodeLinear, bias_add, dense_mm, node_epilogue, sage_dense  # noqa: F401
 from .loss import weighted_cross_entropy  # noqa: F401
 from .softmax import dot_attention, edge_softmax, gatv2_attention  # noqa: F401
-from .glob import SortPooling  # noqa: F401
+from .glob import KNNGraph, SegmentedKNNGraph, SortPooling  # noqa: F401

@@ -14,6 +14,8 @@ the later-DGL module names and arguments) on top of:
 * DotGatConv   : scaled dot-product attention over the in-edges in one kernel
                  (transformer/modules/models.py:79-86, kernel.dot_attention)
 * SAGEConv     : update_all(copy_src, mean) -> g-SpMM mean
+* EdgeConv     : two node products and update_all(copy_src, max) -> the max
+                 g-SpMM (DGCNN's layer over a dgl.knn_graph)
 * RelGraphConv : typed-edge block-diagonal g-SpMM (rgcn/layers.py:121-132), or
                  with regularizer="basis" the dense per-relation weights of
                  the basis layer on the f32 MFMA (rgcn/layers.py:52-100)
@@ -29,7 +31,8 @@ from ... import kernel
 from ...base import DGLError
 from .linear import NodeLinear, sage_dense, bias_add
 
-__all__ = ["GraphConv", "GATConv", "GATv2Conv", "DotGatConv", "SAGEConv", "RelGraphConv"]
+__all__ = ["GraphConv", "GATConv", "GATv2Conv", "DotGatConv", "SAGEConv", "EdgeConv",
+           "RelGraphConv"]
 
 
 class GraphConv(nn.Module):
@@ -197,6 +200,26 @@ class SAGEConv(nn.Module):
         # fc_neigh (no bias) commutes with the mean: the narrower side is
         # aggregated; both products and their sum fused (linear.sage_dense)
         return sage_dense(feat, aggregate, self.fc_self, self.fc_neigh, self.activation)
+
+
+class EdgeConv(nn.Module):
+    """The EdgeConv layer of DGCNN (Wang et al., "Dynamic Graph CNN for
+    Learning on Point Clouds"): h_v = max_{u->v} Theta (x_u - x_v) + Phi x_v,
+    per output channel; a node without in-edges gets Phi x_v - Theta x_v + 0.
+    x_v leaves the max, h_v = max_u (Theta x_u) + (Phi - Theta) x_v: two node
+    products and one copy_u + max g-SpMM, no per-edge product."""
+
+    def __init__(self, in_feats, out_feats, bias=True):
+        super(EdgeConv, self).__init__()
+        self.theta = NodeLinear(in_feats, out_feats, bias=False)
+        self.phi = NodeLinear(in_feats, out_feats, bias=bias)
+
+    def forward(self, g, feat):
+        t = self.theta(feat)
+        g.ndata["_ec_t"] = t
+        g.update_all(fn.copy_src("_ec_t", "_ec_m"), fn.max("_ec_m", "_ec_h"))
+        g.ndata.pop("_ec_t")
+        return g.ndata.pop("_ec_h") + (self.phi(feat) - t)
 
 
 class RelGraphConv(nn.Module):

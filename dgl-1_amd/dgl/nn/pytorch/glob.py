@@ -1,5 +1,6 @@
 """Global pooling over the graphs of a batch (the ``glob`` module later
-releases of the reference added to ``dgl.nn.pytorch``)."""
+releases of the reference added to ``dgl.nn.pytorch``), and the layers that
+make a graph from points (its ``factory`` module)."""
 from __future__ import absolute_import
 
 import torch
@@ -7,8 +8,9 @@ from torch import nn
 
 from ... import kernel
 from ...batched_graph import _topk_segments
+from ...transform import knn_graph, segmented_knn_graph
 
-__all__ = ["SortPooling"]
+__all__ = ["SortPooling", "KNNGraph", "SegmentedKNNGraph"]
 
 
 class SortPooling(nn.Module):
@@ -34,3 +36,29 @@ class SortPooling(nn.Module):
         segs = _topk_segments(graph, "nodes", feat.shape[0])
         values, _ = kernel.segment_topk(feat, segs, self.k, sortby=-1)
         return values.reshape(values.shape[0], -1)
+
+
+class KNNGraph(nn.Module):
+    """Points to their k-nearest-neighbour graph (``dgl.knn_graph``), the
+    graph layer of DGCNN / EdgeConv models, which rebuild it in feature space
+    at every layer: ``forward(x)`` with ``x (N, D)`` or ``(B, N, D)``."""
+
+    def __init__(self, k):
+        super(KNNGraph, self).__init__()
+        self.k = k
+
+    def forward(self, x, exclude_self=False):
+        return knn_graph(x, self.k, exclude_self)
+
+
+class SegmentedKNNGraph(nn.Module):
+    """:class:`KNNGraph` over clouds of unequal sizes
+    (``dgl.segmented_knn_graph``): ``forward(x, segs)`` with ``x (N, D)`` and
+    the list of sizes ``segs``."""
+
+    def __init__(self, k):
+        super(SegmentedKNNGraph, self).__init__()
+        self.k = k
+
+    def forward(self, x, segs, exclude_self=False):
+        return segmented_knn_graph(x, self.k, segs, exclude_self)

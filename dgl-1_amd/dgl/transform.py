@@ -1,20 +1,25 @@
-"""Graph transforms: the line graph and the reverse of a DGLGraph.
+"""Graph transforms: the line graph and the reverse of a DGLGraph, and the
+k-nearest-neighbour graph of a point set.
 
 The surface of the reference's python/dgl/transform.py. The line graph has a
 device route (csrc/line_graph.hip): with ``ctx=`` a ROCm device it is built
 there from the graph's cached adjacency and stays there, so message passing
 over it on that device never builds a native index. ``reverse`` is host
-plumbing only.
+plumbing only. ``knn_graph`` / ``segmented_knn_graph`` (later releases of the
+reference) run on the segment kNN (csrc/segment_knn.hip) where the points are;
+on a ROCm device the edge list stays there like the line graph's.
 """
 from __future__ import absolute_import
 
 import torch
 
+from . import kernel
 from .base import DGLError
 from .batched_graph import BatchedDGLGraph
 from .graph import DGLGraph
+from .graph_index import _DeviceLineGraphIndex
 
-__all__ = ["line_graph", "reverse"]
+__all__ = ["line_graph", "reverse", "knn_graph", "segmented_knn_graph"]
 
 
 def line_graph(g, backtracking=True, shared=False, ctx=None):
@@ -95,3 +100,51 @@ def reverse(g, share_ndata=False, share_edata=False):
     if share_edata:
         rg._edge_frame = g._edge_frame
     return rg
+
+
+def segmented_knn_graph(x, k, segs, exclude_self=False):
+    """The k-nearest-neighbour graph of the points ``x (N, D)`` float32 taken
+    as consecutive clouds of ``segs`` (a list of sizes summing to ``N``)
+    points: a node per point, and edge ``i * k + j`` runs **from** the j-th
+    nearest point of node ``i``'s cloud **to** node ``i``, so every node's
+    predecessors are its neighbours, nearest first, and ``update_all`` pulls
+    from them. Distances, order and ties are kernel.segment_knn's; without
+    ``exclude_self`` a point is its own first neighbour. Every cloud must hold
+    ``k`` candidates (``k + 1`` points with ``exclude_self``), else DGLError.
+
+    For ``x`` on a ROCm device the graph is built and left there (the f32
+    MFMA kernel, no distance matrix): message passing over it on that device
+    never builds a native index. The graph is mutable and never a multigraph;
+    it is not differentiable in ``x``.
+
+    >>> x = torch.tensor([[0.], [1.], [3.], [10.], [12.]])
+    >>> dgl.segmented_knn_graph(x, 2, [3, 2]).edges()
+    (tensor([0, 1, 1, 0, 2, 1, 3, 4, 4, 3]), tensor([0, 0, 1, 1, 2, 2, 3, 3, 4, 4]))
+    """
+    sizes = [int(n) for n in segs]
+    need = int(k) + (1 if exclude_self else 0)
+    if sizes and min(sizes) < need:
+        raise DGLError("every segment needs at least %d points for k = %d%s, got one of %d"
+                       % (need, int(k), " without self" if exclude_self else "", min(sizes)))
+    nbr, _ = kernel.segment_knn(x, sizes, k, exclude_self)
+    N = x.shape[0]
+    src = nbr.reshape(-1)
+    dst = torch.arange(N, dtype=torch.int64, device=x.device).repeat_interleave(nbr.shape[1])
+    if x.is_cuda:
+        return DGLGraph(_DeviceLineGraphIndex(N, src, dst))
+    g = DGLGraph()
+    g.add_nodes(N)
+    g.add_edges(src, dst)
+    return g
+
+
+def knn_graph(x, k, exclude_self=False):
+    """:func:`segmented_knn_graph` of one cloud ``x (N, D)``, or of ``B``
+    clouds of ``N`` points ``x (B, N, D)`` (a graph on ``B * N`` nodes, node
+    ``b * N + i`` being point ``i`` of cloud ``b``)."""
+    if not isinstance(x, torch.Tensor) or x.dim() not in (2, 3):
+        raise DGLError("knn_graph expects (N, D) or (B, N, D) points")
+    if x.dim() == 2:
+        return segmented_knn_graph(x, k, [x.shape[0]], exclude_self)
+    B, N, D = x.shape
+    return segmented_knn_graph(x.reshape(B * N, D), k, [N] * B, exclude_self)

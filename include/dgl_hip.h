@@ -595,6 +595,46 @@ int dglhip_segment_topk_bwd_host(int64_t num_segments, int64_t num_rows, int64_t
                                  const int64_t* indices, float* dx, int num_threads);
 
 /* ------------------------------------------------------------------------ */
+/* Segment k-nearest neighbours (csrc/segment_knn.hip): for every row i of   */
+/* segment s of the points x (float32 [num_rows, dim], row stride ldx >=     */
+/* dim; offsets as for the segment reduction) the k rows j of the same       */
+/* segment with the smallest squared Euclidean distance; what later releases */
+/* of the reference build with knn_graph / segmented_knn_graph.              */
+/* nbr int64 [num_rows, k] holds global row ids, dist float32 [num_rows, k]  */
+/* the squared distances, both ascending by the order below.                 */
+/* Distance, in float32: d(i, j) = n_i + n_j - 2 <x_i, x_j> with n_i =       */
+/* <x_i, x_i>; a value that is not above zero is +0.0, a NaN stays NaN;      */
+/* d(i, i) is +0.0 by definition, and with exclude_self != 0 the pair (i, i) */
+/* is no candidate. Order: ascending by (d, j), NaN after every number: an   */
+/* ascending stable sort. The order is strict, so each form returns the      */
+/* exact top-k under its own distances. A row with fewer than k candidates   */
+/* fills the remaining slots with index -1 and distance +inf.                */
+/* The device's dot products are chains of v_mfma_f32_16x16x4_f32, the       */
+/* host's plain fma chains: the two agree to rounding, and exactly wherever  */
+/* the arithmetic is exact. 1 <= k <= DGLHIP_KNN_MAX_K and 1 <= dim <=       */
+/* DGLHIP_KNN_MAX_DIM (outside: -1 with a message).                          */
+/* ------------------------------------------------------------------------ */
+#define DGLHIP_KNN_MAX_K 64
+#define DGLHIP_KNN_MAX_DIM 256
+/* Bytes of the device form's workspace (the rows' squared norms). */
+int64_t dglhip_segment_knn_workspace_bytes(int64_t num_segments, int64_t num_rows, int64_t dim,
+                                           int64_t k);
+/* Device form: all pointers are device pointers; two launches (the norms,
+ * then one workgroup per 64 query rows of a segment, placed from the offsets
+ * alone). num_rows < 2^31. No host sync, no allocation, no global atomics;
+ * out-of-range offsets are clamped to [0, num_rows], never followed. Rows
+ * that no segment covers are not written. */
+int dglhip_segment_knn_device(int64_t num_segments, int64_t num_rows, int64_t dim, int64_t k,
+                              int exclude_self, const int64_t* offsets, const float* x,
+                              int64_t ldx, int64_t* nbr, float* dist, void* workspace,
+                              void* stream);
+/* Host form (brute force, the thread pool over the rows); offsets validated
+ * as by dglhip_segment_reduce_host. */
+int dglhip_segment_knn_host(int64_t num_segments, int64_t num_rows, int64_t dim, int64_t k,
+                            int exclude_self, const int64_t* offsets, const float* x,
+                            int64_t ldx, int64_t* nbr, float* dist, int num_threads);
+
+/* ------------------------------------------------------------------------ */
 /* Edge softmax (csrc/edge_softmax.hip): the softmax of per-edge scores over */
 /* the edges of each node, and over the nodes or edges of each graph of a    */
 /* batch. The rows of a CSR are the groups: indptr int64[num_rows + 1],      */
