@@ -13,6 +13,7 @@ from . import function  # noqa: F401
 from . import backend  # noqa: F401
 from . import init  # noqa: F401
 from . import kernel  # noqa: F401
+from . import geometry  # noqa: F401
 from .base import ALL, DGLError  # noqa: F401
 from .graph import DGLGraph  # noqa: F401
 from .batched_graph import (BatchedDGLGraph, batch, unbatch, split,  # noqa: F401

@@ -246,6 +246,11 @@ def _load():
                                       [_vp] * 4),
         "dglhip_segment_knn_host": (_c_int, [_c_i64] * 4 + [_c_int, _vp, _vp, _c_i64, _vp, _vp,
                                                             _c_int]),
+        "dglhip_segment_fps_workspace_bytes": (_c_i64, [_c_i64] * 5),
+        "dglhip_segment_fps_device": (_c_int, [_c_i64] * 4 + [_vp, _vp, _c_i64] + [_vp] * 3 +
+                                      [_c_i64, _vp, _vp]),
+        "dglhip_segment_fps_host": (_c_int, [_c_i64] * 4 + [_vp, _vp, _c_i64] + [_vp] * 3 +
+                                    [_c_int]),
         "dglhip_edge_softmax_workspace_bytes": (_c_i64, [_c_i64, _c_i64, _c_i64]),
         "dglhip_edge_softmax_device": (_c_int, [_c_i64, _c_i64, _c_i64] + [_vp] * 5 +
                                        [_c_i64, _vp, _vp]),

@@ -79,8 +79,8 @@ from .gat import (  # noqa: F401
     DOT_ATTENTION_CHUNK, DOT_ATTENTION_BATCH, dot_attention,
     GATV2_CHUNK, GATV2_BATCH, GATV2_BATCH_DFD, GATV2_BATCH_DFS, gatv2_attention)
 from .segment import (  # noqa: F401
-    SEGMENT_CHUNK, TOPK_CHUNK, KNN_MAX_K, KNN_MAX_DIM, SegmentOffsets, segment_reduce,
-    segment_topk, segment_knn)
+    SEGMENT_CHUNK, TOPK_CHUNK, KNN_MAX_K, KNN_MAX_DIM, FPS_MAX_DIM, SegmentOffsets,
+    segment_reduce, segment_topk, segment_knn, segment_fps)
 
 __all__ = ["CSR", "SparseAdj", "build_csr", "gspmm", "gsddmm_dot",
            "MSG_COPY_U", "MSG_U_MUL_E", "MSG_COPY_E", "RED_SUM", "RED_MAX", "RED_MEAN"]

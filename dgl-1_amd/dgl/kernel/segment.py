@@ -1,7 +1,8 @@
 """The segment reduction (csrc/segment_reduce.hip) and the segment top-k
 (csrc/segment_topk.hip): the readouts of a batched graph; and the segment
 k-nearest neighbours (csrc/segment_knn.hip): the graph of a batch of point
-clouds."""
+clouds; and the segment farthest point sampling (csrc/segment_fps.hip): the
+centroids of a batch of point clouds."""
 from __future__ import absolute_import
 
 import numpy as np
@@ -19,6 +20,7 @@ SEGMENT_CHUNK = 1024  # DGLHIP_SEGMENT_CHUNK: rows per chain of the segment redu
 TOPK_CHUNK = 2048  # DGLHIP_TOPK_CHUNK: rows one workgroup ranks in LDS, and the largest k
 KNN_MAX_K = 64  # DGLHIP_KNN_MAX_K: the longest neighbour list of the segment kNN
 KNN_MAX_DIM = 256  # DGLHIP_KNN_MAX_DIM: the most coordinates of its points
+FPS_MAX_DIM = 256  # DGLHIP_FPS_MAX_DIM: the most coordinates of a sampled point
 
 
 class SegmentOffsets(object):
@@ -359,3 +361,89 @@ def segment_knn(x, offsets, k, exclude_self=False):
         check_call(LIB.dglhip_segment_knn_host(
             B, N, D, k, int(bool(exclude_self)), ptr(off), ptr(xv), ldx, ptr(nbr), ptr(dist), 0))
     return nbr, dist
+
+
+# ---------------------------------------------------------------------------
+# Segment farthest point sampling: dgl.geometry (csrc/segment_fps.hip)
+# ---------------------------------------------------------------------------
+def _fps_without_coordinates(segs, m, start, dev):
+    """D == 0: every distance is +0.0, so after the first pick the rows follow
+    in order. From the offsets alone, where they are."""
+    off = segs.on(dev)
+    beg, n = off[:-1, None], (off[1:] - off[:-1])[:, None]
+    st = torch.zeros_like(n) if start is None else \
+        torch.minimum(start[:, None].clamp(min=0), (n - 1).clamp(min=0))
+    j = torch.arange(m, dtype=torch.int64, device=dev)[None, :]
+    row = torch.where(j == 0, st, torch.where(j - 1 < st, j - 1, j))
+    idx = torch.where(j < n, beg + row, torch.full_like(row, -1))
+    dist = torch.zeros(idx.shape, dtype=torch.float32, device=dev)
+    dist[:, 0] = torch.where(n[:, 0] > 0, float("inf"), 0.0)
+    return idx, dist
+
+
+def segment_fps(x, offsets, m, start=None):
+    """Farthest point sampling of every segment ``x[offsets[s] :
+    offsets[s+1]]``: ``(idx, dist)``, ``idx (B, m)`` int64 global row ids in
+    pick order and ``dist (B, m)`` float32, the pick's squared distance to
+    the nearest earlier pick when it was picked (``+inf`` for the first). Not
+    differentiable.
+
+    ``x`` is ``(N, D)`` float32 (read in place through its row stride) with
+    ``D <= FPS_MAX_DIM``, ``offsets`` what :func:`segment_reduce` takes, ``m
+    >= 1``; ``start`` is None (every segment starts at its row 0) or a
+    ``(B,)`` int64 tensor of rows within the segments. A ``start`` on the
+    host is checked against host-side sizes (outside ``[0, rows)`` is a
+    DGLError); one on the device is clamped into its segment.
+
+    In float32, ``d(p, j)`` is the chain ``s = fma(t, t, s)`` over ``t = x_j[c]
+    - x_p[c]``, ``c`` ascending, from ``+0.0``. Every row keeps the minimum of
+    its distances to the picks so far, from ``+inf``; a NaN distance never
+    lowers it. A picked row is never picked again; each later pick is the
+    row with the largest minimum, the lowest row among equals: no tie is left
+    to chance, and a row with a NaN coordinate (whose minimum stays ``+inf``)
+    is picked early. A segment of fewer than ``m`` rows fills the remaining
+    slots with ``-1`` and ``+0.0``. Same bits on the host and on the device,
+    where one workgroup keeps a segment on chip for all ``m`` picks; no
+    atomics, no host synchronisation."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 2:
+        raise DGLError("segment_fps expects an (N, D) tensor of points")
+    if x.dtype != torch.float32:
+        raise DGLError("segment_fps computes in float32, got %s" % x.dtype)
+    m = int(m)
+    if m < 1:
+        raise DGLError("segment_fps picks m >= 1 rows, got m = %d" % m)
+    N, D = x.shape
+    if D > FPS_MAX_DIM:
+        raise DGLError("segment_fps serves D <= FPS_MAX_DIM = %d, got D = %d" % (FPS_MAX_DIM, D))
+    segs = _segment_offsets(offsets)
+    if segs.num_rows >= 0 and segs.num_rows != N:
+        raise DGLError("offsets end at %d, expected the %d rows" % (segs.num_rows, N))
+    B, dev = segs.num_segments, x.device
+    if start is not None:
+        if not isinstance(start, torch.Tensor) or start.dtype != torch.int64 \
+                or tuple(start.shape) != (B,):
+            raise DGLError("start must be an int64 tensor of the %d segments' first picks" % B)
+        if not start.is_cuda and segs.host is not None:
+            n = segs.host[1:] - segs.host[:-1]
+            if bool(((n > 0) & ((start < 0) | (start >= n))).any()):
+                raise DGLError("start names a row outside its segment")
+        start = start.detach().to(dev).contiguous()
+    if N == 0 or B == 0:
+        return (torch.full((B, m), -1, dtype=torch.int64, device=dev),
+                torch.zeros(B, m, dtype=torch.float32, device=dev))
+    if D == 0:
+        return _fps_without_coordinates(segs, m, start, dev)
+    idx = torch.empty(B, m, dtype=torch.int64, device=dev)
+    dist = torch.empty(B, m, dtype=torch.float32, device=dev)
+    off = segs.on(dev)
+    xv, ldx = _rows_view(x.detach(), D)
+    if dev.type == "cuda":
+        nbytes = LIB.dglhip_segment_fps_workspace_bytes(B, N, D, m, segs.max_rows)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+        check_call(LIB.dglhip_segment_fps_device(
+            B, N, D, m, ptr(off), ptr(xv), ldx, ptr(start), ptr(idx), ptr(dist), segs.max_rows,
+            ptr(ws), _stream_of(dev)))
+    else:
+        check_call(LIB.dglhip_segment_fps_host(
+            B, N, D, m, ptr(off), ptr(xv), ldx, ptr(start), ptr(idx), ptr(dist), 0))
+    return idx, dist

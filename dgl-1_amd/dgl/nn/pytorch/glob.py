@@ -8,9 +8,10 @@ from torch import nn
 
 from ... import kernel
 from ...batched_graph import _topk_segments
+from ...geometry import farthest_point_sampler
 from ...transform import knn_graph, segmented_knn_graph
 
-__all__ = ["SortPooling", "KNNGraph", "SegmentedKNNGraph"]
+__all__ = ["SortPooling", "KNNGraph", "SegmentedKNNGraph", "FarthestPointSampler"]
 
 
 class SortPooling(nn.Module):
@@ -62,3 +63,17 @@ class SegmentedKNNGraph(nn.Module):
 
     def forward(self, x, segs, exclude_self=False):
         return segmented_knn_graph(x, self.k, segs, exclude_self)
+
+
+class FarthestPointSampler(nn.Module):
+    """The centroids of a PointNet++ set abstraction
+    (``dgl.geometry.farthest_point_sampler``): ``forward(pos)`` with ``pos (B,
+    N, D)`` returns the ``(B, npoints)`` indices within each cloud, the first
+    being point 0 (or ``start_idx``)."""
+
+    def __init__(self, npoints):
+        super(FarthestPointSampler, self).__init__()
+        self.npoints = npoints
+
+    def forward(self, pos, start_idx=None):
+        return farthest_point_sampler(pos, self.npoints, start_idx)

@@ -635,6 +635,53 @@ int dglhip_segment_knn_host(int64_t num_segments, int64_t num_rows, int64_t dim,
                             int64_t ldx, int64_t* nbr, float* dist, int num_threads);
 
 /* ------------------------------------------------------------------------ */
+/* Segment farthest point sampling (csrc/segment_fps.hip): m rows of every   */
+/* segment of the points x (float32 [num_rows, dim], row stride ldx >= dim;  */
+/* offsets as for the segment reduction), each the row farthest from those   */
+/* picked before it: the sampler that opens a PointNet++ set abstraction.    */
+/* idx int64 [num_segments, m] holds global row ids in pick order, dist      */
+/* float32 [num_segments, m] the pick's squared distance to the nearest      */
+/* earlier pick at the time it was picked; dist[s, 0] is +inf.               */
+/* Distance, in float32: d(p, j) is the chain s = 0; for c ascending: t =    */
+/* x_j[c] - x_p[c]; s = fmaf(t, t, s). Running minimum: mind_j starts at     */
+/* +inf; after picking p, mind_j = d(p, j) < mind_j ? d(p, j) : mind_j, so a */
+/* NaN distance never lowers it. The first pick of segment s is its row      */
+/* start[s] (row 0 when start is NULL); a picked row is taken and never      */
+/* picked again; pick i >= 1 is the untaken row with the largest mind, the   */
+/* lowest row among equals. The order is strict and the chain is the same    */
+/* on both sides: host and device agree bit for bit on every input. (A row   */
+/* with a NaN coordinate keeps mind = +inf and is picked early, lowest row   */
+/* first.) A segment of n < m rows fills slots j >= n with index -1 and      */
+/* +0.0. 1 <= dim <= DGLHIP_FPS_MAX_DIM, m >= 1, num_rows < 2^31 (outside:   */
+/* -1 with a message).                                                       */
+/* ------------------------------------------------------------------------ */
+#define DGLHIP_FPS_MAX_DIM 256
+/* The longest segment the device form keeps on chip for the whole call. */
+#define DGLHIP_FPS_MAX_RESIDENT 8192
+/* Bytes of the device form's workspace (0 when max_segment_rows says that
+ * every segment stays on chip; else the running minima, 4 num_rows). */
+int64_t dglhip_segment_fps_workspace_bytes(int64_t num_segments, int64_t num_rows, int64_t dim,
+                                           int64_t m, int64_t max_segment_rows);
+/* Device form: all pointers are device pointers; one launch, one workgroup
+ * per segment for all m picks. start: NULL or int64[num_segments], the row
+ * within the segment of the first pick, clamped into the segment.
+ * max_segment_rows: the longest segment if the caller knows it from
+ * host-side sizes (it picks the kernel and must not be understated: rows
+ * past it are not sampled), -1 if not. No host sync, no allocation, no
+ * global atomics; out-of-range offsets are clamped to [0, num_rows], never
+ * followed. */
+int dglhip_segment_fps_device(int64_t num_segments, int64_t num_rows, int64_t dim, int64_t m,
+                              const int64_t* offsets, const float* x, int64_t ldx,
+                              const int64_t* start, int64_t* idx, float* dist,
+                              int64_t max_segment_rows, void* workspace, void* stream);
+/* Host form (the plain loop, the thread pool over the segments); offsets
+ * validated as by dglhip_segment_reduce_host, and a start outside [0, rows)
+ * of a segment that has rows is an error. */
+int dglhip_segment_fps_host(int64_t num_segments, int64_t num_rows, int64_t dim, int64_t m,
+                            const int64_t* offsets, const float* x, int64_t ldx,
+                            const int64_t* start, int64_t* idx, float* dist, int num_threads);
+
+/* ------------------------------------------------------------------------ */
 /* Edge softmax (csrc/edge_softmax.hip): the softmax of per-edge scores over */
 /* the edges of each node, and over the nodes or edges of each graph of a    */
 /* batch. The rows of a CSR are the groups: indptr int64[num_rows + 1],      */
