@@ -251,6 +251,11 @@ def _load():
                                       [_c_i64, _vp, _vp]),
         "dglhip_segment_fps_host": (_c_int, [_c_i64] * 4 + [_vp, _vp, _c_i64] + [_vp] * 3 +
                                     [_c_int]),
+        "dglhip_segment_radius_workspace_bytes": (_c_i64, [_c_i64] * 5),
+        "dglhip_segment_radius_device": (_c_int, [_c_i64] * 5 + [_c_float, _c_int] +
+                                         [_vp, _vp, _c_i64] * 2 + [_vp] * 5),
+        "dglhip_segment_radius_host": (_c_int, [_c_i64] * 5 + [_c_float, _c_int] +
+                                       [_vp, _vp, _c_i64] * 2 + [_vp] * 3 + [_c_int]),
         "dglhip_edge_softmax_workspace_bytes": (_c_i64, [_c_i64, _c_i64, _c_i64]),
         "dglhip_edge_softmax_device": (_c_int, [_c_i64, _c_i64, _c_i64] + [_vp] * 5 +
                                        [_c_i64, _vp, _vp]),

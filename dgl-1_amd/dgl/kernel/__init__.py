@@ -28,7 +28,7 @@ spmm -> {rgcn, gat, segment}: ``policy`` (constants, the schedule policy),
 ``plan`` (the views of the native launch plan), ``csr`` (CSR, SparseAdj and
 their builders), ``spmm`` (g-SpMM / g-SDDMM, call timing), ``rgcn``
 (gather_rows, DistMult, the typed-block and typed-linear operators), ``gat`` (edge attention,
-the fused GAT layer, the edge softmax, the fused dot-product attention), ``segment`` (the segment reduction, the segment top-k and the segment kNN). This file only
+the fused GAT layer, the edge softmax, the fused dot-product attention), ``segment`` (the segment reduction, the segment top-k, the segment kNN, the farthest point sampling and the ball query). This file only
 re-exports them, so callers keep ``kernel.<name>``.
 
 A setting that is rebound after import lives in one module, which reads it at
@@ -79,8 +79,9 @@ from .gat import (  # noqa: F401
     DOT_ATTENTION_CHUNK, DOT_ATTENTION_BATCH, dot_attention,
     GATV2_CHUNK, GATV2_BATCH, GATV2_BATCH_DFD, GATV2_BATCH_DFS, gatv2_attention)
 from .segment import (  # noqa: F401
-    SEGMENT_CHUNK, TOPK_CHUNK, KNN_MAX_K, KNN_MAX_DIM, FPS_MAX_DIM, SegmentOffsets,
-    segment_reduce, segment_topk, segment_knn, segment_fps)
+    SEGMENT_CHUNK, TOPK_CHUNK, KNN_MAX_K, KNN_MAX_DIM, FPS_MAX_DIM, RADIUS_MAX_K,
+    RADIUS_MAX_DIM, SegmentOffsets, segment_reduce, segment_topk, segment_knn, segment_fps,
+    segment_radius)
 
 __all__ = ["CSR", "SparseAdj", "build_csr", "gspmm", "gsddmm_dot",
            "MSG_COPY_U", "MSG_U_MUL_E", "MSG_COPY_E", "RED_SUM", "RED_MAX", "RED_MEAN"]

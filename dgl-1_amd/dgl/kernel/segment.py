@@ -2,7 +2,8 @@
 (csrc/segment_topk.hip): the readouts of a batched graph; and the segment
 k-nearest neighbours (csrc/segment_knn.hip): the graph of a batch of point
 clouds; and the segment farthest point sampling (csrc/segment_fps.hip): the
-centroids of a batch of point clouds."""
+centroids of a batch of point clouds; and the segment fixed-radius neighbours
+(csrc/segment_radius.hip): the ball query round those centroids."""
 from __future__ import absolute_import
 
 import numpy as np
@@ -21,6 +22,9 @@ TOPK_CHUNK = 2048  # DGLHIP_TOPK_CHUNK: rows one workgroup ranks in LDS, and the
 KNN_MAX_K = 64  # DGLHIP_KNN_MAX_K: the longest neighbour list of the segment kNN
 KNN_MAX_DIM = 256  # DGLHIP_KNN_MAX_DIM: the most coordinates of its points
 FPS_MAX_DIM = 256  # DGLHIP_FPS_MAX_DIM: the most coordinates of a sampled point
+RADIUS_MAX_K = 64  # DGLHIP_RADIUS_MAX_K: the longest member list of the ball query
+RADIUS_MAX_DIM = 16  # DGLHIP_RADIUS_MAX_DIM: the most coordinates of its points
+_RADIUS_EXCLUDE_SELF, _RADIUS_PAD_FIRST = 1, 2  # DGLHIP_RADIUS_*: the flags
 
 
 class SegmentOffsets(object):
@@ -447,3 +451,84 @@ def segment_fps(x, offsets, m, start=None):
         check_call(LIB.dglhip_segment_fps_host(
             B, N, D, m, ptr(off), ptr(xv), ldx, ptr(start), ptr(idx), ptr(dist), 0))
     return idx, dist
+
+
+# ---------------------------------------------------------------------------
+# Segment fixed-radius neighbours: ball_query, radius_graph (csrc/segment_radius.hip)
+# ---------------------------------------------------------------------------
+def segment_radius(x, offsets, r, k, q=None, q_offsets=None, exclude_self=False,
+                   pad_first=False):
+    """For every query row ``i`` of every segment ``q[q_offsets[s] :
+    q_offsets[s+1]]`` the first ``k`` rows ``j`` of ``x[offsets[s] :
+    offsets[s+1]]``, in row order, closer than ``r``: ``(nbr, cnt, dist)``,
+    ``nbr (M, k)`` int64 global rows of ``x``, ``cnt (M,)`` int32 ``min(members,
+    k)`` and ``dist (M, k)`` float32 squared distances. Not differentiable.
+
+    ``x (N, D)`` and ``q (M, D)`` are float32 (read in place through their row
+    strides), ``offsets`` and ``q_offsets`` what :func:`segment_reduce` takes,
+    with the same number of segments; ``q=None`` searches ``x`` round its own
+    rows (the graph case). ``1 <= k <= RADIUS_MAX_K`` and ``D <=
+    RADIUS_MAX_DIM``; outside is an error, not another path.
+
+    In float32, ``d(i, j)`` is the chain ``s = fma(t, t, s)`` over ``t = x_j[c]
+    - q_i[c]``, ``c`` ascending, from ``+0.0``; ``j`` is a member when ``d <
+    float32(r) * float32(r)``, strictly (a NaN distance is outside), and with
+    ``exclude_self`` not when it is the query's own global row. The members
+    are the first ``k`` in row order, not the nearest. Slots past ``cnt[i]``
+    hold ``-1`` and ``+inf``, with ``pad_first`` the first member and its
+    distance (PointNet++'s grouping); a query without a member keeps ``-1`` and
+    ``+inf``. Same bits on the host and on the device, where a workgroup
+    walks a cloud once for 64 queries and stops when all of them are full: no
+    distance matrix, no atomics, no host synchronisation."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 2:
+        raise DGLError("segment_radius expects an (N, D) tensor of points")
+    if q is None:
+        if q_offsets is not None:
+            raise DGLError("q_offsets without q")
+        q, q_offsets = x, offsets
+    elif q_offsets is None:
+        raise DGLError("queries need their own q_offsets")
+    if not isinstance(q, torch.Tensor) or q.dim() != 2 or q.shape[1] != x.shape[1]:
+        raise DGLError("segment_radius expects (M, D) queries of the points' width")
+    if x.dtype != torch.float32 or q.dtype != torch.float32:
+        raise DGLError("segment_radius computes in float32, got %s and %s" % (x.dtype, q.dtype))
+    if q.device != x.device:
+        raise DGLError("points on %s, queries on %s" % (x.device, q.device))
+    k = int(k)
+    if k < 1 or k > RADIUS_MAX_K:
+        raise DGLError("segment_radius serves 1 <= k <= RADIUS_MAX_K = %d, got k = %d"
+                       % (RADIUS_MAX_K, k))
+    (N, D), M = x.shape, q.shape[0]
+    if D > RADIUS_MAX_DIM:
+        raise DGLError("segment_radius serves D <= RADIUS_MAX_DIM = %d, got D = %d"
+                       % (RADIUS_MAX_DIM, D))
+    segs = _segment_offsets(offsets)
+    qsegs = segs if q_offsets is offsets else _segment_offsets(q_offsets)
+    if segs.num_rows >= 0 and segs.num_rows != N:
+        raise DGLError("offsets end at %d, expected the %d rows" % (segs.num_rows, N))
+    if qsegs.num_rows >= 0 and qsegs.num_rows != M:
+        raise DGLError("q_offsets end at %d, expected the %d queries" % (qsegs.num_rows, M))
+    if qsegs.num_segments != segs.num_segments:
+        raise DGLError("%d segments of points, %d of queries"
+                       % (segs.num_segments, qsegs.num_segments))
+    B, dev = segs.num_segments, x.device
+    r2 = np.float32(r) * np.float32(r)
+    nbr = torch.full((M, k), -1, dtype=torch.int64, device=dev)
+    cnt = torch.zeros(M, dtype=torch.int32, device=dev)
+    dist = torch.full((M, k), float("inf"), dtype=torch.float32, device=dev)
+    if N == 0 or M == 0 or B == 0:
+        return nbr, cnt, dist
+    if D == 0:  # no storage to point the library at: every distance is +0.0
+        x, q, D = x.new_zeros(N, 1), q.new_zeros(M, 1), 1
+    flags = (_RADIUS_EXCLUDE_SELF if exclude_self else 0) | (_RADIUS_PAD_FIRST if pad_first else 0)
+    xv, ldx = _rows_view(x.detach(), D)
+    qv, ldq = (xv, ldx) if q is x else _rows_view(q.detach(), D)
+    if dev.type == "cuda":
+        check_call(LIB.dglhip_segment_radius_device(
+            B, N, M, D, k, r2, flags, ptr(segs.on(dev)), ptr(xv), ldx, ptr(qsegs.on(dev)),
+            ptr(qv), ldq, ptr(nbr), ptr(cnt), ptr(dist), None, _stream_of(dev)))
+    else:
+        check_call(LIB.dglhip_segment_radius_host(
+            B, N, M, D, k, r2, flags, ptr(segs.on(dev)), ptr(xv), ldx, ptr(qsegs.on(dev)),
+            ptr(qv), ldq, ptr(nbr), ptr(cnt), ptr(dist), 0))
+    return nbr, cnt, dist

@@ -7,4 +7,6 @@ from .conv import DotGatConv, EdgeConv, GATConv, GATv2Conv, GraphConv, RelGraphC
 from .linear import NodeLinear, bias_add, dense_mm, node_epilogue, sage_dense  # noqa: F401
 from .loss import weighted_cross_entropy  # noqa: F401
 from .softmax import dot_attention, edge_softmax, gatv2_attention  # noqa: F401
-from .glob import FarthestPointSampler, KNNGraph, SegmentedKNNGraph, SortPooling  # noqa: F401
+from .glob import (  # noqa: F401
+    FarthestPointSampler, FixedRadiusNearNeighbors, KNNGraph, RadiusGraph, SegmentedKNNGraph,
+    SortPooling)

@@ -8,10 +8,11 @@ from torch import nn
 
 from ... import kernel
 from ...batched_graph import _topk_segments
-from ...geometry import farthest_point_sampler
-from ...transform import knn_graph, segmented_knn_graph
+from ...geometry import ball_query, farthest_point_sampler
+from ...transform import knn_graph, radius_graph, segmented_knn_graph
 
-__all__ = ["SortPooling", "KNNGraph", "SegmentedKNNGraph", "FarthestPointSampler"]
+__all__ = ["SortPooling", "KNNGraph", "SegmentedKNNGraph", "RadiusGraph", "FarthestPointSampler",
+           "FixedRadiusNearNeighbors"]
 
 
 class SortPooling(nn.Module):
@@ -65,6 +66,21 @@ class SegmentedKNNGraph(nn.Module):
         return segmented_knn_graph(x, self.k, segs, exclude_self)
 
 
+class RadiusGraph(nn.Module):
+    """Points to their cutoff graph (``dgl.radius_graph``), the graph layer of
+    the molecular and mesh models built on a distance cutoff: ``forward(x)``
+    with ``x (N, D)`` or ``(B, N, D)``."""
+
+    def __init__(self, r, max_num_neighbors=32, self_loop=False):
+        super(RadiusGraph, self).__init__()
+        self.r = r
+        self.max_num_neighbors = max_num_neighbors
+        self.self_loop = self_loop
+
+    def forward(self, x):
+        return radius_graph(x, self.r, self.max_num_neighbors, self.self_loop)
+
+
 class FarthestPointSampler(nn.Module):
     """The centroids of a PointNet++ set abstraction
     (``dgl.geometry.farthest_point_sampler``): ``forward(pos)`` with ``pos (B,
@@ -77,3 +93,20 @@ class FarthestPointSampler(nn.Module):
 
     def forward(self, pos, start_idx=None):
         return farthest_point_sampler(pos, self.npoints, start_idx)
+
+
+class FixedRadiusNearNeighbors(nn.Module):
+    """The grouping of a PointNet++ set abstraction
+    (``dgl.geometry.ball_query``): ``forward(pos, centroids)`` with ``pos (B, N,
+    D)`` and the ``(B, M)`` indices a :class:`FarthestPointSampler` returns (or
+    ``(B, M, D)`` points) gives the ``(B, M, n_neighbor)`` indices within each
+    cloud of the first ``n_neighbor`` points closer than ``radius``, padded
+    with the first."""
+
+    def __init__(self, radius, n_neighbor):
+        super(FixedRadiusNearNeighbors, self).__init__()
+        self.radius = radius
+        self.n_neighbor = n_neighbor
+
+    def forward(self, pos, centroids):
+        return ball_query(pos, centroids, self.radius, self.n_neighbor)

@@ -8,6 +8,8 @@ over it on that device never builds a native index. ``reverse`` is host
 plumbing only. ``knn_graph`` / ``segmented_knn_graph`` (later releases of the
 reference) run on the segment kNN (csrc/segment_knn.hip) where the points are;
 on a ROCm device the edge list stays there like the line graph's.
+``radius_graph`` / ``segmented_radius_graph`` do the same on the segment
+fixed-radius search (csrc/segment_radius.hip).
 """
 from __future__ import absolute_import
 
@@ -19,7 +21,8 @@ from .batched_graph import BatchedDGLGraph
 from .graph import DGLGraph
 from .graph_index import _DeviceLineGraphIndex
 
-__all__ = ["line_graph", "reverse", "knn_graph", "segmented_knn_graph"]
+__all__ = ["line_graph", "reverse", "knn_graph", "segmented_knn_graph", "radius_graph",
+           "segmented_radius_graph"]
 
 
 def line_graph(g, backtracking=True, shared=False, ctx=None):
@@ -148,3 +151,48 @@ def knn_graph(x, k, exclude_self=False):
         return segmented_knn_graph(x, k, [x.shape[0]], exclude_self)
     B, N, D = x.shape
     return segmented_knn_graph(x.reshape(B * N, D), k, [N] * B, exclude_self)
+
+
+def segmented_radius_graph(x, r, segs, max_num_neighbors=32, self_loop=False):
+    """The cutoff graph of the points ``x (N, D)`` float32 taken as
+    consecutive clouds of ``segs`` (a list of sizes summing to ``N``) points:
+    a node per point and an edge **from** every point ``j`` of node ``i``'s
+    cloud closer than ``r`` **to** node ``i``. Node ``i``'s edges are
+    consecutive and ascending in ``j``; a node with more than
+    ``max_num_neighbors`` points inside keeps the first that many in point
+    order (not the nearest). ``self_loop`` keeps the edge ``(i, i)``.
+    Distances and membership are kernel.segment_radius's.
+
+    For ``x`` on a ROCm device the graph is built and left there (the ball
+    query in HIP, then a boolean index over its slots): message passing over
+    it on that device never builds a native index. The graph is mutable and
+    never a multigraph; it is not differentiable in ``x``.
+
+    >>> x = torch.tensor([[0.], [1.], [3.], [10.], [12.]])
+    >>> dgl.segmented_radius_graph(x, 2.5, [3, 2]).edges()
+    (tensor([1, 0, 2, 1, 4, 3]), tensor([0, 1, 1, 2, 3, 4]))
+    """
+    nbr, cnt, _ = kernel.segment_radius(x, [int(n) for n in segs], r, max_num_neighbors,
+                                        exclude_self=not self_loop)
+    N, k = nbr.shape
+    valid = torch.arange(k, device=x.device)[None, :] < cnt[:, None]
+    src = nbr[valid]
+    dst = torch.arange(N, dtype=torch.int64, device=x.device)[:, None].expand(N, k)[valid]
+    if x.is_cuda:
+        return DGLGraph(_DeviceLineGraphIndex(N, src, dst))
+    g = DGLGraph()
+    g.add_nodes(N)
+    g.add_edges(src, dst)
+    return g
+
+
+def radius_graph(x, r, max_num_neighbors=32, self_loop=False):
+    """:func:`segmented_radius_graph` of one cloud ``x (N, D)``, or of ``B``
+    clouds of ``N`` points ``x (B, N, D)`` (a graph on ``B * N`` nodes, node
+    ``b * N + i`` being point ``i`` of cloud ``b``)."""
+    if not isinstance(x, torch.Tensor) or x.dim() not in (2, 3):
+        raise DGLError("radius_graph expects (N, D) or (B, N, D) points")
+    if x.dim() == 2:
+        return segmented_radius_graph(x, r, [x.shape[0]], max_num_neighbors, self_loop)
+    B, N, D = x.shape
+    return segmented_radius_graph(x.reshape(B * N, D), r, [N] * B, max_num_neighbors, self_loop)

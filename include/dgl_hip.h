@@ -682,6 +682,53 @@ int dglhip_segment_fps_host(int64_t num_segments, int64_t num_rows, int64_t dim,
                             const int64_t* start, int64_t* idx, float* dist, int num_threads);
 
 /* ------------------------------------------------------------------------ */
+/* Segment fixed-radius neighbours (csrc/segment_radius.hip): the ball query */
+/* that groups points round the centroids of a PointNet++ set abstraction,   */
+/* and with q = x the builder of radius_graph. x: float32 [num_rows, dim],   */
+/* row stride ldx >= dim, x_offsets int64[num_segments + 1]; q: float32      */
+/* [num_queries, dim], row stride ldq >= dim, q_offsets int64[num_segments + */
+/* 1]. Query segment s searches candidate segment s only.                    */
+/* Distance, in float32: d(i, j) is the chain s = +0.0; for c ascending: t = */
+/* x_j[c] - q_i[c]; s = fmaf(t, t, s); the same explicit fmaf on both sides, */
+/* so host and device agree bit for bit on every input. Membership: d < r2,  */
+/* strictly; a NaN distance is outside. With DGLHIP_RADIUS_EXCLUDE_SELF the  */
+/* candidate whose global row equals the query's global row is skipped       */
+/* (meaningful when q is x with the same offsets). Selection: the first k    */
+/* members in ascending candidate row, not the nearest k.                    */
+/* nbr int64 [num_queries, k]: global rows of x; cnt int32 [num_queries]:    */
+/* min(members, k); dist float32 [num_queries, k] or NULL. Slots past cnt[i] */
+/* hold -1 / +inf; with DGLHIP_RADIUS_PAD_FIRST the first member and its     */
+/* distance (a query without a member keeps -1 / +inf).                      */
+/* 1 <= k <= DGLHIP_RADIUS_MAX_K, 1 <= dim <= DGLHIP_RADIUS_MAX_DIM,         */
+/* num_rows and num_queries < 2^31 (outside: -1 with a message).             */
+/* ------------------------------------------------------------------------ */
+#define DGLHIP_RADIUS_MAX_K 64
+#define DGLHIP_RADIUS_MAX_DIM 16
+#define DGLHIP_RADIUS_EXCLUDE_SELF 1
+#define DGLHIP_RADIUS_PAD_FIRST 2
+/* Bytes of the device form's workspace: 0, the lists live on chip. */
+int64_t dglhip_segment_radius_workspace_bytes(int64_t num_segments, int64_t num_rows,
+                                              int64_t num_queries, int64_t dim, int64_t k);
+/* Device form: all pointers are device pointers; one launch, one workgroup
+ * per 64 queries of a segment, placed from the query offsets alone. No host
+ * sync, no allocation, no global atomics; out-of-range offsets are clamped to
+ * [0, rows], never followed. Queries that no segment covers are not written.
+ * workspace may be NULL. */
+int dglhip_segment_radius_device(int64_t num_segments, int64_t num_rows, int64_t num_queries,
+                                 int64_t dim, int64_t k, float r2, int flags,
+                                 const int64_t* x_offsets, const float* x, int64_t ldx,
+                                 const int64_t* q_offsets, const float* q, int64_t ldq,
+                                 int64_t* nbr, int32_t* cnt, float* dist, void* workspace,
+                                 void* stream);
+/* Host form (the plain loop per query, the thread pool over the queries);
+ * both offset arrays validated as by dglhip_segment_reduce_host. */
+int dglhip_segment_radius_host(int64_t num_segments, int64_t num_rows, int64_t num_queries,
+                               int64_t dim, int64_t k, float r2, int flags,
+                               const int64_t* x_offsets, const float* x, int64_t ldx,
+                               const int64_t* q_offsets, const float* q, int64_t ldq,
+                               int64_t* nbr, int32_t* cnt, float* dist, int num_threads);
+
+/* ------------------------------------------------------------------------ */
 /* Edge softmax (csrc/edge_softmax.hip): the softmax of per-edge scores over */
 /* the edges of each node, and over the nodes or edges of each graph of a    */
 /* batch. The rows of a CSR are the groups: indptr int64[num_rows + 1],      */
